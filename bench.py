@@ -14,7 +14,14 @@ step is `device_ms_per_step`.  The Solve is sequential in pod order, so
 data-path collective): weak scaling; value = sum of checks over ranks / max
 step time.
 
-Every BASELINE config has a leg with its own roofline and CPU baseline:
+A plain run (`--gpus 1 --steps N --warmup W`) does what the headline needs and
+no more: it builds the CM problem, warms up, times the N steps, writes the last
+step's result under --dump-outputs when asked, and prints the result line.
+Everything below (whole-call latency, the CPU baselines and their bit-exact
+comparisons, the other configs and legs, the per-leg detail file) runs with
+--full; --only <leg> other than cm needs --full.
+
+With --full every BASELINE config has a leg with its own roofline and CPU baseline:
   configs.C1/C2/C3  provisioning Solve legs (same step definition as CM)
   consolidation     C4: SingleNodeConsolidation over 5,000 state nodes
                     (sharded round-robin over ranks, commands all-gathered
@@ -127,6 +134,59 @@ def roofline(kernel, algo_bytes, avg_ms, traffic=None, peak=HBM_PEAK_GBS, bound=
 def digest(res_dict):
     import hashlib
     return hashlib.sha256(json.dumps(res_dict, sort_keys=True, separators=(",", ":")).encode()).hexdigest()
+
+
+# ------------------------------------------------------------ --dump-outputs
+def result_arrays_f64(result):
+    """the Solve result a caller of the timed path receives (Solver.fetch()
+    after the last timed gs_run), as flat float64 arrays: every value is a
+    uint32 index, a byte or an int64 quantity below 2^53, so float64 holds it
+    exactly.  CSR lists carry their offsets; the requirement strings are the
+    UTF-8 bytes of the per-claim strings joined by NUL; the requests matrix has
+    one column per resource name in sorted order."""
+    claims = result["claims"]
+    names = sorted({k for c in claims for k in c["requests"]})
+
+    def csr(lists):
+        off = np.zeros(len(lists) + 1, dtype=np.float64)
+        off[1:] = np.cumsum([len(x) for x in lists])
+        flat = np.array([v for x in lists for v in x], dtype=np.float64)
+        return off, flat
+
+    cpo, cp = csr([c["pods"] for c in claims])
+    cio, ci = csr([c["its"] for c in claims])
+    npo, npods = csr(result["nodes"])
+    req = np.zeros((len(claims), len(names)), dtype=np.float64)
+    for i, c in enumerate(claims):
+        for k, v in c["requests"].items():
+            req[i, names.index(k)] = v
+    text = "\0".join(c["requirements"] for c in claims).encode()
+    return {
+        "claim_nodepool": np.array([c["nodepool"] for c in claims], dtype=np.float64),
+        "claim_pod_offsets": cpo, "claim_pods": cp,
+        "claim_it_offsets": cio, "claim_its": ci,
+        "claim_requests": req,
+        "claim_requirements_utf8": np.frombuffer(text, dtype=np.uint8).astype(np.float64),
+        "node_pod_offsets": npo, "node_pods": npods,
+        "error_pods": np.array(result["errors"], dtype=np.float64),
+    }
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, result):
+    """DIR/<name>.npy for every array of the last timed step's result that
+    holds anything: a list the caller receives empty (CM has no existing
+    nodes, so no node pods) has no file, and a build that fills it shows up
+    as a file the other run lacks"""
+    arrays = {k: a for k, a in result_arrays_f64(result).items() if a.size}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: the result holds {total} bytes, over the {DUMP_MAX_BYTES} byte budget")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 # ------------------------------------------------------------ output lines
@@ -309,7 +369,7 @@ def solve_leg(problem, solver, steps, warmup, latency_steps, barrier=None, max_o
     names = {"feas": "feas_kernel", "ffd": "ffdw_kernel" if solver.flags == 0 and len(problem.nodes) <= 6144
              else "ffd_kernel"}
     ph = np.mean(np.array(phases), axis=0) if phases else np.zeros(8)
-    return {
+    out_leg = {
         "ms_per_step": elapsed * 1e3 / steps,
         "checks": problem.checks(),
         "device_kernel_ms": {k: round(v, 4) for k, v in kms.items()},
@@ -348,6 +408,9 @@ def solve_leg(problem, solver, steps, warmup, latency_steps, barrier=None, max_o
                                                 traffic_of(traffic or {}, leg, "feas", "feas_cursor")),
         "_result": out,
     }
+    if not phases:  # no whole-call latency was timed: no phase split to report
+        out_leg["solve_latency_phases_ms"] = None
+    return out_leg
 
 
 def cpu_baseline_solve(problem, got):
@@ -797,11 +860,17 @@ def solver_filter_ms(solver):
 
 
 # --------------------------------------------------------------------- main
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline's timed CM steps: whole-call latency, the CPU baselines and their "
+                         "bit-exact comparisons, every other config and leg, the per-leg detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's Solve result (what Solver.fetch() returns) as "
+                         "DIR/<name>.npy, float64; the same arguments give the same inputs on every run")
     ap.add_argument("--pods", type=int, default=100_000)
     ap.add_argument("--latency-steps", type=int, default=3)
     ap.add_argument("--c4-nodes", type=int, default=5000)
@@ -822,9 +891,25 @@ def main():
                                                  "ranking (profiling passes)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "r6", "traffic.json"),
                     help="PMC-derived HBM bytes per launch per leg (tools/pmc_traffic.py, committed under profiles/)")
-    ap.add_argument("--detail-json", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
-                    help="the whole record (every leg); stdout's last line is the compact headline")
-    args = ap.parse_args()
+    ap.add_argument("--detail-json", default=None,
+                    help="the whole record (every leg); stdout's last line is the compact headline "
+                         "(with --full the default is bench_out/bench_detail.json in the repository)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        # the plain run: the headline's CM leg alone, nothing timed or checked beside its steps
+        if args.only not in (None, "cm"):
+            ap.error(f"--only {args.only} needs --full")
+        args.only = "cm"
+        args.latency_steps = 0
+    elif args.detail_json is None:
+        args.detail_json = os.path.join(ROOT, "bench_out", "bench_detail.json")
+    return args
+
+
+def main():
+    args = parse_args()
 
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -875,6 +960,8 @@ def main():
                       barrier, max_over_ranks, traffic, "cm")
         solver.close()
         result = r.pop("_result")
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, result)
         ms = r.pop("ms_per_step")
         line.update({
             "value": r["checks"] * world / (ms * 1e-3),

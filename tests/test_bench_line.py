@@ -8,6 +8,8 @@ import os
 import sys
 from contextlib import redirect_stdout
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -126,3 +128,93 @@ def test_strong_scaling_section_gloo_world2():
     line["strong_scaling"] = sec
     h = bench.headline(line)
     assert h["strong_scaling"] == sec and len(json.dumps(h)) <= bench.HEADLINE_MAX_BYTES
+
+
+# ------------------------------------------- the plain run, --full, --dump-outputs
+def test_plain_run_is_the_cm_leg_alone_and_full_keeps_every_leg():
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert plain.steps == 7 and plain.warmup == 3 and not plain.full
+    assert plain.only == "cm" and plain.latency_steps == 0 and plain.detail_json is None
+    assert bench.parse_args(["--only", "cm"]).only == "cm"
+    full = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3", "--full"])
+    assert full.only is None and full.latency_steps == 3 and not full.no_cpu_baseline
+    assert full.detail_json.endswith(os.path.join("bench_out", "bench_detail.json"))
+    assert bench.parse_args(["--full", "--only", "c4", "--detail-json", "x.json"]).detail_json == "x.json"
+    for bad in (["--only", "c4"], ["--steps", "0"], ["--warmup", "-1"]):
+        try:
+            bench.parse_args(bad)
+        except SystemExit as e:
+            assert e.code == 2
+        else:
+            raise AssertionError(bad)
+
+
+_RESULT = {
+    "claims": [
+        {"nodepool": 0, "pods": [4, 0, 2], "its": [7, 1], "requirements": "zone|In|a,b|-|-|0\nk|Exists||3|-|0",
+         "requests": {"cpu": 2500, "memory": (1 << 52) + 1}},
+        {"nodepool": 1, "pods": [3], "its": [5], "requirements": "", "requests": {"cpu": 100, "pods": 1}},
+    ],
+    "nodes": [[], [1, 5]],
+    "errors": [6],
+}
+
+
+def test_dump_outputs_writes_the_result_exactly(tmp_path):
+    import numpy as np
+    d = tmp_path / "out" / "run0"
+    bench.dump_outputs(str(d), _RESULT)
+    got = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_MAX_BYTES
+    lists = lambda off, flat: [[int(v) for v in flat[int(a):int(b)]] for a, b in zip(off[:-1], off[1:])]  # noqa: E731
+    assert lists(got["claim_pod_offsets"], got["claim_pods"]) == [c["pods"] for c in _RESULT["claims"]]
+    assert lists(got["claim_it_offsets"], got["claim_its"]) == [c["its"] for c in _RESULT["claims"]]
+    assert lists(got["node_pod_offsets"], got["node_pods"]) == _RESULT["nodes"]
+    assert got["claim_nodepool"].tolist() == [0, 1] and got["error_pods"].tolist() == [6]
+    # columns: cpu, memory, pods (sorted names); int64 quantities survive float64
+    assert got["claim_requests"].astype(np.int64).tolist() == [[2500, (1 << 52) + 1, 0], [100, 0, 1]]
+    text = bytes(got["claim_requirements_utf8"].astype(np.uint8)).decode()
+    assert text.split("\0") == [c["requirements"] for c in _RESULT["claims"]]
+    # no file is empty: a list the caller receives empty is left out, its offsets stay
+    assert all(a.size for a in got.values())
+    no_nodes = dict(_RESULT, nodes=[], errors=[])
+    bench.dump_outputs(str(tmp_path / "no_nodes"), no_nodes)
+    assert sorted(set(os.listdir(d)) - set(os.listdir(tmp_path / "no_nodes"))) == ["error_pods.npy", "node_pods.npy"]
+    assert np.load(tmp_path / "no_nodes" / "node_pod_offsets.npy").tolist() == [0.0]
+
+
+@pytest.mark.gpu
+def test_gpu_plain_run_times_its_steps_and_dumps_the_last_result(tmp_path):
+    """bench.py as a process: a plain run reports the steps it was asked for
+    and nothing beside the headline leg; --dump-outputs holds the Solve result
+    of the same seeded problem, identical from run to run"""
+    import subprocess
+    import numpy as np
+    from gpusched import synth
+    from gpusched.lib import Solver
+    pods = 3000
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--pods", str(pods), "--dump-outputs", str(tmp_path / "dump")],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = r.stdout.strip().splitlines()
+    assert len(out) == 1  # no leg lines
+    h = json.loads(out[0])
+    assert h["metric"] == bench.METRIC and h["unit"] == "checks/s" and h["higher_is_better"] is True
+    assert h["dtype"] == "int64" and h["steps"] == 3 and h["warmup"] == 1 and h["ms_per_step"] > 0
+    assert h["config"]["pods"] == pods
+    assert abs(h["value"] - h["config"]["checks_per_step"] / (h["ms_per_step"] * 1e-3)) <= 1e-5 * h["value"]
+    assert h["cpu_baseline"] is None and h["solve_latency_ms"] is None and "legs" not in h and "detail_file" not in h
+    s = Solver(0)
+    try:
+        want, _ = s.solve(synth.make_cm(n_pods=pods, seed=0x5EED0006))
+    finally:
+        s.close()
+    want = {k: a for k, a in bench.result_arrays_f64(want).items() if a.size}
+    assert "node_pods" not in want  # CM has no existing nodes
+    got = {f[:-4]: np.load(tmp_path / "dump" / f) for f in os.listdir(tmp_path / "dump")}
+    assert sorted(got) == sorted(want)
+    for k in want:
+        assert got[k].dtype == np.float64 and np.array_equal(got[k], want[k]), k
+    assert len(want["claim_pods"]) + len(want["error_pods"]) == pods

@@ -11,7 +11,7 @@ timeout -k 10 420 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 tail -3 $O/pytest_gpu.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 cat $O/smoke.log
-timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err
 head -c 600 $O/bench.json; echo
 if [ "${1:-}" = "prof" ]; then
   bash $R/tools/profile_round.sh

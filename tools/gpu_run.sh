@@ -7,8 +7,8 @@
 #   suite          whole -m gpu suite + smoke
 #   tests:<expr>   pytest -m gpu -k <expr>
 #   file:<path>    pytest -m gpu on one test file
-#   bench          the default bench line (+ per-leg detail json)
-#   only:<leg>     bench.py --only <leg> (5 steps)
+#   bench          the bench line of bench.py --full (+ per-leg detail json)
+#   only:<leg>     bench.py --full --only <leg> (5 steps)
 #   ffd            tools/ffd_diag.py FFD device ms on cm / c3 / e2e / c2
 #   prof           tools/profile_round.sh (kernel stats + PMC traffic)
 #   sqpmc          SQ instruction / stall counters of the wave Solve on CM, two
@@ -41,11 +41,11 @@ for step in "$@"; do
       timeout -k 10 600 $PYT $f > $O/pytest_$b.log 2>&1
       tail -3 $O/pytest_$b.log ;;
     bench)
-      timeout -k 10 600 python -u bench.py --detail-json $O/bench_detail.json > $O/bench.out 2> $O/bench.err
+      timeout -k 10 600 python -u bench.py --full --detail-json $O/bench_detail.json > $O/bench.out 2> $O/bench.err
       tail -c 700 $O/bench.out ;;
     only:*)
       leg=${step#only:}
-      timeout -k 10 300 python -u bench.py --only $leg --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_$leg$LS.out 2> $O/bench_$leg$LS.err
+      timeout -k 10 300 python -u bench.py --full --only $leg --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_$leg$LS.out 2> $O/bench_$leg$LS.err
       tail -c 400 $O/bench_$leg$LS.out ;;
     ffd)
       timeout -k 10 400 python -u tools/ffd_diag.py > $O/ffd_diag.txt 2>&1
