@@ -227,7 +227,9 @@ extern "C" gs_status gs_rank_instance_types(uint32_t n, const int64_t* cpu_milli
   return GS_OK;
 }
 
-// Test hook (not in gpusched.h; tests/test_wave_sort.py binds it): the
+// TEST-ONLY hooks, both of them: gs_debug_go_sort and gs_debug_go_sort_known
+// are not in gpusched.h, no product path calls them, and only
+// tests/test_wave_sort.py binds them.  They run the
 // single-wave sort.Slice restatement (WaveSort, the Solve's NodeClaim sort)
 // over n u16 keys on the current device; perm[k] = the input index that lands
 // at position k.  Parity with Go's pdqsort is checked against the oracle's
@@ -236,11 +238,26 @@ extern "C" gs_status gs_debug_go_sort_known(const uint16_t* keys, uint32_t n, in
 extern "C" gs_status gs_debug_go_sort(const uint16_t* keys, uint32_t n, uint32_t* perm) {
   return gs_debug_go_sort_known(keys, n, -1, perm);
 }
-// ... with x: the caller states that every position but x is in order (the
-// Solve's one-change sorts), so the first partition takes partition_known
+// ... with x >= 0: the caller states that every position but x is in order
+// (the Solve's one-change sorts), so the first partition takes
+// partition_known, which searches the boundary on that premise.  The
+// statement is checked here on the host, before any device call: x outside
+// [-1, n), or keys that are not non-decreasing once position x is removed,
+// are GS_E_INVALID.  x = -1 states nothing.
 extern "C" gs_status gs_debug_go_sort_known(const uint16_t* keys, uint32_t n, int32_t x, uint32_t* perm) {
   if (n && (!keys || !perm)) return GS_E_INVALID;
   if (n > GS_RANK_MAX) return GS_E_CAPACITY;
+  if (x < -1 || (x >= 0 && (uint32_t)x >= n)) return GS_E_INVALID;
+  if (x >= 0) {
+    bool have = false;
+    uint16_t prev = 0;
+    for (uint32_t k = 0; k < n; k++) {
+      if (k == (uint32_t)x) continue;
+      if (have && keys[k] < prev) return GS_E_INVALID;
+      prev = keys[k];
+      have = true;
+    }
+  }
   if (n == 0) return GS_OK;
   std::vector<uint16_t> h((size_t)n * 2);
   for (uint32_t k = 0; k < n; k++) {

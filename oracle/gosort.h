@@ -26,9 +26,20 @@ struct XorShift {
 
 enum Hint { kUnknown = 0, kIncreasing = 1, kDecreasing = 2 };
 
+// Branch counters of one or more slice() calls (instrumentation for the
+// sort-path tests).  Counting only: no comparison or swap depends on them, so
+// the permutation is the same with and without.
+struct Counters {
+  uint64_t heap_sort = 0, partition_equal = 0, break_patterns = 0, reverse_range = 0;
+  uint64_t hint[3] = {0, 0, 0};  // choose_pivot results by Hint
+  uint64_t partial_true = 0, partial_false = 0;  // partial_insertion_sort's return
+  int first_hint = -1;  // the last slice()'s first choose_pivot hint (-1: none ran)
+};
+
 template <class D>
 struct Sorter {
   D& d;  // d.less(i,j), d.swap(i,j)
+  Counters* c = nullptr;
 
   void insertion_sort(int a, int b) {
     for (int i = a + 1; i < b; i++)
@@ -46,6 +57,7 @@ struct Sorter {
     }
   }
   void heap_sort(int a, int b) {
+    if (c) c->heap_sort++;
     int first = a, lo = 0, hi = b - a;
     for (int i = (hi - 1) / 2; i >= 0; i--) sift_down(i, hi, first);
     for (int i = hi - 1; i >= 0; i--) {
@@ -78,7 +90,9 @@ struct Sorter {
         hint = kIncreasing;
       }
       if (wasBalanced && wasPartitioned && hint == kIncreasing) {
-        if (partial_insertion_sort(a, b)) return;
+        const bool done = partial_insertion_sort(a, b);
+        if (c) (done ? c->partial_true : c->partial_false)++;
+        if (done) return;
       }
       if (a > 0 && !d.less(a - 1, pivot)) {
         int mid = partition_equal(a, b, pivot);
@@ -127,6 +141,7 @@ struct Sorter {
     return j;
   }
   int partition_equal(int a, int b, int pivot) {
+    if (c) c->partition_equal++;
     d.swap(a, pivot);
     int i = a + 1, j = b - 1;
     for (;;) {
@@ -164,6 +179,7 @@ struct Sorter {
   }
   void break_patterns(int a, int b) {
     int length = b - a;
+    if (c) c->break_patterns++;
     if (length >= 8) {
       XorShift r{(uint64_t)length};
       uint64_t modulus = 1ull << bits_len((uint64_t)length);
@@ -191,6 +207,10 @@ struct Sorter {
     if (swaps == 0) *hint = kIncreasing;
     else if (swaps == maxSwaps) *hint = kDecreasing;
     else *hint = kUnknown;
+    if (c) {
+      c->hint[*hint]++;
+      if (c->first_hint < 0) c->first_hint = *hint;
+    }
     return j;
   }
   void order2(int& a, int& b, int* swaps) {
@@ -209,6 +229,7 @@ struct Sorter {
   }
   int median_adjacent(int a, int* swaps) { return median(a - 1, a, a + 1, swaps); }
   void reverse_range(int a, int b) {
+    if (c) c->reverse_range++;
     int i = a, j = b - 1;
     while (i < j) {
       d.swap(i, j);
@@ -220,8 +241,9 @@ struct Sorter {
 
 // sort.Slice(x, less): limit = bits.Len(uint(length))
 template <class D>
-void slice(D& d, int n) {
-  Sorter<D> s{d};
+void slice(D& d, int n, Counters* c = nullptr) {
+  if (c) c->first_hint = -1;
+  Sorter<D> s{d, c};
   s.pdqsort(0, n, bits_len((uint64_t)n));
 }
 

@@ -27,6 +27,41 @@ extern "C" {
  * Result memory is owned by the oracle until the next call. */
 gs_status oracle_solve(const gs_problem* problem, gs_result* out);
 
+/* Mutant of oracle_solve for the sort-path tests: the same Solve, except that
+ * the per-pod NodeClaim sort is std::stable_sort on pod count instead of Go's
+ * unstable sort.Slice.  A scenario whose result differs from oracle_solve's
+ * depends on Go's tie order.  The choice is an argument of this one call; it
+ * leaves nothing behind for a later oracle_solve. */
+gs_status oracle_solve_stable_ties(const gs_problem* problem, gs_result* out);
+
+/* Which paths of Go's sort.Slice the NodeClaim sorts (scheduler.go add()) of
+ * the last oracle_solve / oracle_solve_stable_ties / oracle_consolidate
+ * reached; reset at the start of each such call, summed over a
+ * consolidation's simulations.  Every sort is classified before it runs, by
+ * its length M (buckets <=12, 13-49, 50-64, >64) and by the state of the
+ * array: sorted; exactly one descent (x, x+1) with neither x nor x+1 in
+ * {q, 2q, 3q}, q = M/4 ("untouched"); exactly one descent with x or x+1 among
+ * them ("touched": choosePivot's sampled triples see it); more descents.
+ * Writes min(n, ORACLE_SP_N) words. */
+enum {
+  ORACLE_SP_HIST = 0,             /* [4 M buckets][4 states: sorted, untouched, touched, multi] */
+  ORACLE_SP_POS = 16,             /* [4 M buckets][6]: touched sorts by x = q-1, q, 2q-1, 2q, 3q-1, 3q */
+  ORACLE_SP_HEAP_SORT = 40,       /* gosort.h branch counters: calls */
+  ORACLE_SP_PARTITION_EQUAL = 41,
+  ORACLE_SP_BREAK_PATTERNS = 42,
+  ORACLE_SP_REVERSE_RANGE = 43,
+  ORACLE_SP_HINT = 44,            /* [3] choose_pivot results: unknown, increasing, decreasing */
+  ORACLE_SP_PARTIAL_TRUE = 47,    /* partial_insertion_sort returned true / false */
+  ORACLE_SP_PARTIAL_FALSE = 48,
+  ORACLE_SP_FULL_PDQ = 49,        /* unsorted, M > 12, and M < 50 or the first choosePivot hint not "increasing" */
+  ORACLE_SP_ONE_ROTATION = 50,    /* unsorted, M >= 50 and the first choosePivot hint "increasing" */
+  ORACLE_SP_SORTS = 51,           /* sort.Slice calls */
+  ORACLE_SP_TAIL = 52,            /* [4 M buckets] exactly one descent, at x = M-2: an appended NodeClaim out of
+                                     order (or the last but one raised) */
+  ORACLE_SP_N = 56
+};
+void oracle_last_sort_paths(uint64_t* out, uint32_t n);
+
 /* static per (pod, nodepool) feasibility: a fresh NodeClaim for the pod */
 gs_status oracle_feasibility(const gs_problem* problem, gs_feas_result* out);
 

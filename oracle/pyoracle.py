@@ -55,6 +55,10 @@ def lib():
         L = C.CDLL(LIB)
         L.oracle_solve.argtypes = [C.POINTER(abi.GsProblem), C.POINTER(abi.GsResult)]
         L.oracle_solve.restype = C.c_int
+        L.oracle_solve_stable_ties.argtypes = [C.POINTER(abi.GsProblem), C.POINTER(abi.GsResult)]
+        L.oracle_solve_stable_ties.restype = C.c_int
+        L.oracle_last_sort_paths.argtypes = [C.POINTER(C.c_uint64), C.c_uint32]
+        L.oracle_last_sort_paths.restype = None
         L.oracle_feasibility.argtypes = [C.POINTER(abi.GsProblem), C.POINTER(abi.GsFeasResult)]
         L.oracle_feasibility.restype = C.c_int
         L.oracle_convert_profile.argtypes = [C.POINTER(OracleProfile), C.POINTER(OracleEnv),
@@ -90,6 +94,47 @@ def solve(problem):
     if st != abi.GS_OK:
         return st, None, res
     return st, abi.result_to_dict(res, problem), res
+
+
+def solve_stable_ties(problem):
+    """the mutant Solve whose NodeClaim sort is a stable sort on pod count
+    (oracle.h oracle_solve_stable_ties): a scenario whose result differs from
+    solve()'s depends on Go's tie order"""
+    res = abi.GsResult()
+    st = lib().oracle_solve_stable_ties(C.byref(problem.struct), C.byref(res))
+    if st != abi.GS_OK:
+        return st, None, res
+    return st, abi.result_to_dict(res, problem), res
+
+
+SORT_M_BUCKETS = ("le12", "13_49", "50_64", "gt64")
+SORT_STATES = ("sorted", "untouched", "touched", "multi")
+SORT_POSITIONS = ("q-1", "q", "2q-1", "2q", "3q-1", "3q")
+_SP_N = 56  # oracle.h ORACLE_SP_N
+
+
+def last_sort_paths():
+    """oracle_last_sort_paths as a dict: which paths of Go's sort.Slice the
+    NodeClaim sorts of the last solve() / solve_stable_ties() / consolidate()
+    reached.  "hist"[M bucket][state] and "positions"[M bucket][x] count the
+    sorts as classified before they ran, "tail"[M bucket] those whose one
+    descent is at the array's end (an appended NodeClaim out of order); the
+    rest are gosort.h's branch counters.  "full_pdq" / "one_rotation" split the unsorted sorts of more
+    than 12 NodeClaims by whether Go runs the whole pdqsort or
+    partialInsertionSort's single rotation."""
+    a = (C.c_uint64 * _SP_N)()
+    lib().oracle_last_sort_paths(a, _SP_N)
+    v = [int(x) for x in a]
+    out = {"hist": {b: {s: v[bi * 4 + si] for si, s in enumerate(SORT_STATES)}
+                    for bi, b in enumerate(SORT_M_BUCKETS)},
+           "positions": {b: {x: v[16 + bi * 6 + xi] for xi, x in enumerate(SORT_POSITIONS)}
+                         for bi, b in enumerate(SORT_M_BUCKETS)}}
+    for i, k in enumerate(("heap_sort", "partition_equal", "break_patterns", "reverse_range", "hint_unknown",
+                           "hint_increasing", "hint_decreasing", "partial_true", "partial_false", "full_pdq",
+                           "one_rotation", "sorts")):
+        out[k] = v[40 + i]
+    out["tail"] = {b: v[52 + bi] for bi, b in enumerate(SORT_M_BUCKETS)}
+    return out
 
 
 def last_groups_created():

@@ -1481,6 +1481,44 @@ struct Scheduler {
     return true;
   }
 
+  // instrumentation (oracle.h ORACLE_SP_*): the sort.Slice(newNodeClaims)
+  // calls classified before they run, and gosort.h's branch counters
+  uint64_t sort_paths[ORACLE_SP_N] = {};
+  gosort::Counters sort_ctr;
+  bool stable_ties = false;  // oracle_solve_stable_ties: the mutant sort
+  bool classify_sort() {  // true: the array is not sorted
+    const int M = (int)claims.size();
+    const int bucket = M <= 12 ? 0 : M < 50 ? 1 : M <= 64 ? 2 : 3;
+    int descents = 0, x = -1;
+    for (int i = 0; i + 1 < M; i++)
+      if (claims[i + 1]->pods.size() < claims[i]->pods.size()) {
+        descents++;
+        if (x < 0) x = i;
+      }
+    const int q = M / 4;
+    int pos = -1;
+    if (descents == 1)
+      for (int t = 1; t <= 3; t++) {
+        if (x + 1 == t * q) pos = 2 * (t - 1);
+        else if (x == t * q) pos = 2 * (t - 1) + 1;
+      }
+    const int state = descents == 0 ? 0 : descents > 1 ? 3 : pos < 0 ? 1 : 2;
+    sort_paths[ORACLE_SP_HIST + bucket * 4 + state]++;
+    if (state == 2) sort_paths[ORACLE_SP_POS + bucket * 6 + pos]++;
+    if (descents == 1 && x == M - 2) sort_paths[ORACLE_SP_TAIL + bucket]++;
+    sort_paths[ORACLE_SP_SORTS]++;
+    return descents > 0;
+  }
+  void finish_sort_paths() {
+    sort_paths[ORACLE_SP_HEAP_SORT] = sort_ctr.heap_sort;
+    sort_paths[ORACLE_SP_PARTITION_EQUAL] = sort_ctr.partition_equal;
+    sort_paths[ORACLE_SP_BREAK_PATTERNS] = sort_ctr.break_patterns;
+    sort_paths[ORACLE_SP_REVERSE_RANGE] = sort_ctr.reverse_range;
+    for (int h = 0; h < 3; h++) sort_paths[ORACLE_SP_HINT + h] = sort_ctr.hint[h];
+    sort_paths[ORACLE_SP_PARTIAL_TRUE] = sort_ctr.partial_true;
+    sort_paths[ORACLE_SP_PARTIAL_FALSE] = sort_ctr.partial_false;
+  }
+
   uint64_t claim_calls = 0, node_calls = 0;  // CanAdd calls (instrumentation)
   bool add(Pod& pod) {
     for (uint32_t ni : st.node_order) {
@@ -1504,7 +1542,18 @@ struct Scheduler {
       bool less(int i, int j) { return c[i]->pods.size() < c[j]->pods.size(); }
       void swap(int i, int j) { std::swap(c[i], c[j]); }
     } d{claims};
-    gosort::slice(d, (int)claims.size());
+    const bool unsorted = classify_sort();
+    if (stable_ties) {
+      std::stable_sort(claims.begin(), claims.end(),
+                       [](const NodeClaim* a, const NodeClaim* b) { return a->pods.size() < b->pods.size(); });
+    } else {
+      const int M = (int)claims.size();
+      gosort::slice(d, M, &sort_ctr);
+      if (unsorted && M > 12) {
+        const bool one = M >= 50 && sort_ctr.first_hint == gosort::kIncreasing;
+        sort_paths[one ? ORACLE_SP_ONE_ROTATION : ORACLE_SP_FULL_PDQ]++;
+      }
+    }
     for (auto* nc : claims) {
       Reqs r;
       vector<const InstanceType*> its;
@@ -1634,10 +1683,15 @@ struct ResultStore {
 ResultStore g_res;
 OracleState* g_state = nullptr;
 uint64_t g_groups_created = 0;  // the last oracle_solve's groups created by Topology.Update
+uint64_t g_sort_paths[ORACLE_SP_N] = {};  // the last call's NodeClaim sort paths (oracle_last_sort_paths)
 
-}  // namespace
+void add_sort_paths(Scheduler& s) {
+  s.finish_sort_paths();
+  for (int i = 0; i < ORACLE_SP_N; i++) g_sort_paths[i] += s.sort_paths[i];
+}
 
-extern "C" gs_status oracle_solve(const gs_problem* problem, gs_result* out) {
+gs_status solve_impl(const gs_problem* problem, gs_result* out, bool stable_ties) {
+  std::memset(g_sort_paths, 0, sizeof g_sort_paths);
   auto t0 = std::chrono::steady_clock::now();
   delete g_state;
   g_state = new OracleState();
@@ -1650,7 +1704,9 @@ extern "C" gs_status oracle_solve(const gs_problem* problem, gs_result* out) {
   }
   const double build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   Scheduler s{st};
+  s.stable_ties = stable_ties;
   auto errors = s.solve();
+  add_sort_paths(s);
   ResultStore& r = g_res;
   r = ResultStore();
   r.claim_pod_offsets.push_back(0);
@@ -1706,6 +1762,20 @@ extern "C" gs_status oracle_solve(const gs_problem* problem, gs_result* out) {
   g_groups_created = s.groups_created_in_solve;
   out->t_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return GS_OK;
+}
+
+}  // namespace
+
+extern "C" gs_status oracle_solve(const gs_problem* problem, gs_result* out) {
+  return solve_impl(problem, out, false);
+}
+
+extern "C" gs_status oracle_solve_stable_ties(const gs_problem* problem, gs_result* out) {
+  return solve_impl(problem, out, true);
+}
+
+extern "C" void oracle_last_sort_paths(uint64_t* out, uint32_t n) {
+  for (uint32_t i = 0; i < n && i < (uint32_t)ORACLE_SP_N; i++) out[i] = g_sort_paths[i];
 }
 
 // instrumentation for the KATs: spread groups the last oracle_solve created
@@ -1913,6 +1983,7 @@ gs_command simulate(const gs_consolidation* in, const vector<uint32_t>& cands, c
   b.build();
   Scheduler s{st};
   auto errors = s.solve();
+  add_sort_paths(s);
   // Results.TruncateInstanceTypes(MaxInstanceTypes): a NodeClaim whose top 60
   // by OrderByPrice miss a minValues requirement is dropped, its pods become
   // pod errors
@@ -2031,6 +2102,7 @@ vector<uint32_t> filter_out_same_type(const gs_consolidation* in, const OracleSt
 extern "C" gs_status oracle_consolidate(const gs_consolidation* in, gs_consolidation_result* out, int32_t* chosen_out,
                                         uint32_t* multi_opts, uint32_t* n_multi_opts) {
   if (!in || !in->cluster || !out) return GS_E_INVALID;
+  std::memset(g_sort_paths, 0, sizeof g_sort_paths);
   OracleState base;
   vector<vector<uint32_t>> sets;
   uint32_t mx = 0;

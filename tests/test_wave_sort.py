@@ -153,6 +153,39 @@ def test_random_keys(seed):
     check(rng.integers(0, 65535, size=n))
 
 
+def test_known_position_is_checked_on_the_host():
+    """CPU: gs_debug_go_sort_known's x is a statement about the keys (every
+    position but x in order), and partition_known searches on that premise.
+    The hook checks it before any device call, so a false statement is
+    GS_E_INVALID with or without a device; x = -1 states nothing and passes
+    the check."""
+    from gpusched import abi, lib
+    L = lib.load()
+    f = L.gs_debug_go_sort_known
+    f.argtypes = [C.POINTER(C.c_uint16), C.c_uint32, C.c_int32, C.POINTER(C.c_uint32)]
+    f.restype = C.c_int
+
+    def status(keys, x):
+        n = len(keys)
+        return f((C.c_uint16 * max(1, n))(*keys), n, x, (C.c_uint32 * max(1, n))())
+
+    keys = raised([(3, 40), (4, 60)], 17)  # position 17 alone is out of order
+    for x in (0, 16, 18, 39, 40, 99):  # a wrong x
+        assert status(keys, x) == abi.GS_E_INVALID, x
+    for x in (100, 101, 4096, 2**31 - 1):  # x >= n
+        assert status(keys, x) == abi.GS_E_INVALID, x
+    assert status(keys, -2) == abi.GS_E_INVALID
+    two = list(keys)
+    two[70] += 1  # two positions out of order: no x makes the statement true
+    for x in (17, 70):
+        assert status(two, x) == abi.GS_E_INVALID, x
+    assert status([5, 4], 2) == abi.GS_E_INVALID
+    # accepted by the check (what a valid call returns depends on the device)
+    assert status(keys, -1) != abi.GS_E_INVALID
+    assert status(keys, 17) != abi.GS_E_INVALID
+    assert status(sorted(keys), 99) != abi.GS_E_INVALID
+
+
 def test_heapsort_inputs_reach_heapsort_on_the_oracle():
     """CPU: the committed inputs do reach Go's heapSort fallback (the Python
     restatement in make_heapsort_inputs.py counts it), and the oracle's
