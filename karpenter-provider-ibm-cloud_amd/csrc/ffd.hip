@@ -1231,11 +1231,7 @@ __global__ __launch_bounds__(NT, SIM ? sim_waves_per_eu(NT) : 1) void ffd_kernel
       // fast accept (simple pods): NodeClaim.Add changes only the requests, so
       // a claim whose threshold cursors do not move keeps its (non-empty)
       // options -- CanAdd holds without reading the claim (room test in LDS)
-#ifdef GS_NO_FAST
-      bool simple = false;
-#else
       bool simple = !TOPO && (vr.ctb & VF_SIMPLE);
-#endif
 #pragma unroll
       for (uint32_t r = 4; r < RR; r++) simple = simple && rq[r] == 0;  // room covers resources 0..3
       // ---------------------- in-flight NodeClaims, first that CanAdd wins
@@ -1307,9 +1303,6 @@ __global__ __launch_bounds__(NT, SIM ? sim_waves_per_eu(NT) : 1) void ffd_kernel
         TL(7);
         if (pos < M) {
           if (lp && !fa && !skip_full && pos < mfa) {
-#ifdef GS_ASM_MARK
-            asm volatile("; MARK_FULL_BEGIN");
-#endif
             // one 64-B header read (four 16-B loads): totals, cursors, masks
             const ClaimRec* cr = dd.c_rec + cb + j;
             uint32_t cur[RR];
@@ -1489,9 +1482,6 @@ __global__ __launch_bounds__(NT, SIM ? sim_waves_per_eu(NT) : 1) void ffd_kernel
           }
           if (tid == 0) atomicAdd((unsigned long long*)&S.dbg[13], (unsigned long long)(__builtin_amdgcn_s_memtime() - c0));
         }
-#endif
-#ifdef GS_ASM_MARK
-        asm volatile("; MARK_FULL_END");
 #endif
         const uint64_t pm = __ballot(pre);
         if ((tid & 63) == 0 && pm) atomicAdd((unsigned long long*)&S.cand_full, (unsigned long long)__popcll(pm));
@@ -2076,8 +2066,9 @@ __global__ __launch_bounds__(256) void queue_records_kernel(DevProblem d) {
 
 // qrun[k]: how many records from k on (at most the ring's 16) equal record k
 // in every dword the wave Solve's run mode compares (all but the pod and the
-// variant index): the batch of a run's pods reads it from the ring
-// (ffd_wave.hpp GS_RUN_BATCH) instead of comparing 16 staged records.  One
+// variant index): the run batch read it from the ring instead of comparing
+// 16 staged records.  The batch was rejected and removed; this
+// launch, qrun and the ring lane that carries it are still to go.  One
 // comparison per adjacent pair (same[x]: record x equals record x + 1) into
 // LDS, block range plus a 15-entry halo, then a scan of at most 15 bits
 __device__ __forceinline__ bool queue_record_same(const DevProblem& d, uint32_t a, uint32_t b) {

@@ -105,8 +105,8 @@ extern "C" __global__ __launch_bounds__(64) void rank_sort_kernel(uint16_t* keys
 }
 
 // x: a position known to be the only one out of order (the test hook's
-// one-change inputs take WaveSort::partition_known whatever the Solve's
-// GS_KNOWN_PARTITION), or -1 (the ranking)
+// one-change inputs take WaveSort::partition_known, as the Solve's do), or
+// -1 (the ranking)
 extern "C" hipError_t gsk_rank_sort(uint16_t* keys, uint16_t* pos, const uint32_t* np, uint32_t cap, int x, hipStream_t s) {
   const size_t lds = (size_t)cap * sizeof(uint32_t) + (size_t)(cap + 2) * sizeof(uint16_t);
   hipLaunchKernelGGL(rank_sort_kernel, dim3(1), dim3(64), lds, s, keys, pos, np, cap, x);

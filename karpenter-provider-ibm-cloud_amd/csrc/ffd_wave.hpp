@@ -52,9 +52,6 @@ static_assert(offsetof(VarRec, fk_begin) == 4 && offsetof(VarRec, fk_count) == 8
 static_assert(offsetof(ClaimRec, maxa) == 128, "ClaimRec maxa after two 64-B lines");
 
 constexpr uint32_t WREG = 4;  // option words a scoring lane keeps in registers
-#ifndef GS_ADD_LANES  // experiment builds: 0 = the winner lane updates every option word
-#define GS_ADD_LANES 1
-#endif
 // solver <-> memory-agent wave channels (LDS)
 #ifndef GS_RING
 #define GS_RING 16
@@ -71,21 +68,6 @@ constexpr uint64_t SWAR_HI = 0x8000800080008000ull;  // top bit of each 16-bit c
 enum : uint32_t { MOD_NONE = 0, MOD_INC = 1, MOD_APPEND = 2 };
 #ifndef GS_WAVE_SEQ
 #define GS_WAVE_SEQ 32
-#endif
-// GS_KNOWN_PARTITION: the first partition of a one-change sort searches the
-// boundary (known_partition, out of line) instead of counting every key; 0
-// never, 1 every instantiation, 2 the topology ones.  Bit-exact (the GPU
-// suite; tests/test_wave_sort.py's one-change inputs through the rank
-// kernel's instantiation, which always has it).  Inlined into the sort it
-// changed the CM kernel's code shape (59.5 -> 60.7 KB) and CM got slower
-// (268.7 -> 273.5 ms); out of line the kernel keeps its shape: same session
-// CM 268.7 -> 264.6, E2E 243.4 -> 238.4, C3 383.3 -> 381.6 ms
-// (profiles/r6/known_partition_ab.txt)
-#ifndef GS_KNOWN_PARTITION
-#define GS_KNOWN_PARTITION 1
-#endif
-#ifndef GS_REG_SORT  // 1: sort frames of <= 64 NodeClaims in registers (RegSort); 0: lane 0 over LDS (<= SEQ)
-#define GS_REG_SORT 1
 #endif
 
 // GS_FFD_TL (diagnostic build): shader cycles per pod-loop segment into Ctrl.dbg
@@ -178,7 +160,8 @@ __device__ __forceinline__ uint32_t wave_max_dpp(uint32_t x) {
 // sort.Slice(newNodeClaims, len(Pods) asc) over the packed order: the block
 // restatement of pdqsort_func (ffd.hip Blk) with one wave, so every block
 // reduction is a ballot and every barrier an in-order LDS queue.  Ranges up
-// to SEQ elements run the sequential port on lane 0.
+// to 64 elements are sorted in registers (reg_pdq_frame; lane 0 sorting them
+// over LDS measured slower).
 // partition of the whole array [0, n) when the caller knows its shape:
 // every position but x (the NodeClaim the last Add raised, or the appended
 // one) holds a non-decreasing sequence.  After swap(0, pivot) the positions
@@ -456,9 +439,6 @@ struct WaveSort {
     return c;
   }
   static constexpr int MASK_MAX = 64 * 64;  // positions the lanes' chunk masks cover
-#ifndef GS_MASK_LISTS  // experiment builds: 0 = the two compaction passes instead
-#define GS_MASK_LISTS 1
-#endif
   // a partition's two misplaced lists from the lanes' masks of [lo, lo + n):
   // x < nl is the left side, misplaced where the predicate fails (ascending
   // positions to scr[0 ..]); x >= nl the right side, misplaced where it holds
@@ -517,7 +497,7 @@ struct WaveSort {
     const int mid = a + (int)count_split<false>(a + 1, b, p, luni, runi, &mk);
     PTL(1);
     uint32_t s;
-    if (GS_MASK_LISTS && b - a - 1 <= MASK_MAX) {
+    if (b - a - 1 <= MASK_MAX) {
       s = lists_from_masks(a + 1, (uint32_t)(mid - a), (uint32_t)(b - a - 1), mk);
     } else {
       s = compact(a + 1, mid + 1, false, scr, [&](int k) { return key(k) >= p; });
@@ -542,7 +522,7 @@ struct WaveSort {
     uint64_t mk;
     const int mid = a + (int)count_split<true>(a + 1, b, p, &luni, runi, &mk);
     uint32_t s;
-    if (GS_MASK_LISTS && b - a - 1 <= MASK_MAX) {
+    if (b - a - 1 <= MASK_MAX) {
       s = lists_from_masks(a + 1, (uint32_t)(mid - a), (uint32_t)(b - a - 1), mk);
     } else {
       s = compact(a + 1, mid + 1, false, scr, [&](int k) { return key(k) > p; });
@@ -669,9 +649,6 @@ struct WaveSort {
     }
     wsyncT<G>();
   }
-#ifndef GS_UNIFORM  // experiment builds: 0 = no equal-key frame shortcut
-#define GS_UNIFORM 1
-#endif
 #ifdef GS_SORT_TL
   // diagnostic: shader cycles per part of the generic sort (lane 0 sums into stl[])
   uint64_t* stl = nullptr;
@@ -686,20 +663,15 @@ struct WaveSort {
   do {         \
   } while (0)
 #endif
-  // x: the one position known to break the order (GS_KNOWN_PARTITION: the
-  // first partition then runs partition_known), or -1
+  // x: the one position known to break the order (the first partition then
+  // runs partition_known), or -1
   __device__ __forceinline__ void pdqsort_body(int n, int x = -1) const {
 #ifdef GS_SORT_TL
     uint64_t t_last_ = __builtin_amdgcn_s_memtime();
 #endif
     const SeqSortT<PackedAccT<U32>> seq{{so}};
-    if (GS_REG_SORT ? n <= 64 : n <= SEQ) {
-      if (GS_REG_SORT) {
-        reg_pdq_frame(PackedArr<U32, G>{so}, 0, n, bits_len((uint64_t)n), 1, 1);
-      } else {
-        if (lane == 0) seq.pdq_frame(Frame{0, n, bits_len((uint64_t)n), 1, 1});
-        wsyncT<G>();
-      }
+    if (n <= 64) {
+      reg_pdq_frame(PackedArr<U32, G>{so}, 0, n, bits_len((uint64_t)n), 1, 1);
       return;
     }
     int sp = 0;
@@ -717,13 +689,8 @@ struct WaveSort {
         f.uni = __builtin_amdgcn_readfirstlane(f.uni);
         const int length = f.b - f.a;
         STL(6);  // frame bookkeeping
-        if (GS_REG_SORT ? length <= 64 : length <= SEQ) {
-          if (GS_REG_SORT) {
-            reg_pdq_frame(PackedArr<U32, G>{so}, f.a, f.b, f.limit, f.wb, f.wp);
-          } else {
-            if (lane == 0) seq.pdq_frame(f);
-            wsyncT<G>();
-          }
+        if (length <= 64) {
+          reg_pdq_frame(PackedArr<U32, G>{so}, f.a, f.b, f.limit, f.wb, f.wp);
           STL(0);
           break;
         }
@@ -739,7 +706,7 @@ struct WaveSort {
           f.limit--;
           STL(0);
         }
-        if (GS_UNIFORM && f.uni) {
+        if (f.uni) {
           // every key in [a, b) is equal (swaps keep it so): choosePivot makes
           // no swap (hint increasing, pivot the middle sample), a partial
           // insertion sort finds no inversion, partitionEqual takes the whole
@@ -838,74 +805,6 @@ __device__ int WaveSort<SEQ, U32, U16, G, KNOWN>::partition_known(int n, int piv
   return kp.mid;
 }
 
-// The run batch's placement (GS_RUN_BATCH, the pod loop below): out of line,
-// so its registers do not weigh on the rest of the loop.  Pods 2..k of the
-// batch (lane j < k: pod bp / variant bv) join the claims U_1..U_{k-1} at
-// lanes fl + 1..; returns the window after the k - 1 rotations
-struct RunWin {
-  uint32_t ow, wtok;
-  uint64_t wsl, wrm;
-};
-template <uint32_t RR>
-__device__ __noinline__ RunWin run_batch_place(RunWin w, uint64_t rq, uint32_t bp, uint32_t bv, uint32_t fl, uint32_t m,
-                                               uint32_t k, uint32_t nlog, uint32_t rqn, LogRec* log, ClaimRec* c_rec) {
-  const uint32_t lane = threadIdx.x & 63u;
-  fl = __builtin_amdgcn_readfirstlane(fl);
-  m = __builtin_amdgcn_readfirstlane(m);
-  k = __builtin_amdgcn_readfirstlane(k);
-  nlog = __builtin_amdgcn_readfirstlane(nlog);
-  rqn = __builtin_amdgcn_readfirstlane(rqn);
-  // lane j < k: its pod's log entry (claim U_j); lanes 4i + r:
-  // pod i + 2's request r into U_{i+1}'s totals
-  const uint32_t cj = (uint32_t)__shfl((int)w.ow, (int)((fl + lane) & 63u)) >> 16;
-  if (lane >= 1 && lane < k) log[nlog + lane - 1] = LogRec{bp, bv, cj, 0};
-  {
-    const uint32_t j = 1u + (lane >> 2), r = lane & 3u;
-    const uint32_t ci = (uint32_t)__shfl((int)w.ow, (int)((fl + j) & 63u)) >> 16;
-    const int64_t rqr = (int64_t)shfl_u64(rq, r);
-    if (j < k && r < RR && rqr != 0)
-      atomicAdd((unsigned long long*)&c_rec[ci].tot_lo[r], (unsigned long long)rqr);
-  }
-  // lanes 4i + r re-quantize resource r of U_{i+1} (as this
-  // pod's lanes r did for U_0), packed across the quad with
-  // DPP and moved back to U_{i+1}'s lane
-  {
-    const uint32_t i = lane >> 2, r = lane & 3u, src_l = (fl + 1u + i) & 63u;
-    const uint64_t rm_i = shfl_u64(w.wrm, src_l), sl_i = shfl_u64(w.wsl, src_l);
-    uint32_t q_rm = 0, q_sl = 0;
-    if (r < rqn) {
-      const int64_t rqr = (int64_t)shfl_u64(rq, r);
-      q_rm = qcode_floor(qcode_value((uint32_t)(rm_i >> (16 * r)) & 0xFFFFu) - rqr);
-      q_sl = qcode_ceil(qcode_value((uint32_t)(sl_i >> (16 * r)) & 0xFFFFu) - rqr);
-    }
-    uint32_t prm2 = (lane & 1u) ? q_rm << 16 : q_rm, psl2 = (lane & 1u) ? q_sl << 16 : q_sl;
-    prm2 |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)prm2, 0xB1, 0xF, 0xF, false);  // quad_perm [1,0,3,2]
-    psl2 |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)psl2, 0xB1, 0xF, 0xF, false);
-    const uint32_t hrm2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)prm2, 0x102, 0xF, 0xF, false);  // row_shl:2
-    const uint32_t hsl2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)psl2, 0x102, 0xF, 0xF, false);
-    // lane 4i now holds U_{i+1}'s packed codes (lo dword, hi dword)
-    const uint32_t back = 4u * ((lane - fl - 1u) & 15u);
-    const uint32_t rm_lo = (uint32_t)__shfl((int)prm2, (int)back), rm_hi = (uint32_t)__shfl((int)hrm2, (int)back);
-    const uint32_t sl_lo = (uint32_t)__shfl((int)psl2, (int)back), sl_hi = (uint32_t)__shfl((int)hsl2, (int)back);
-    if (lane > fl && lane < fl + k) {
-      w.wrm = ((uint64_t)rm_hi << 32) | rm_lo;
-      w.wsl = ((uint64_t)sl_hi << 32) | sl_lo;
-      w.ow = w.ow + 1u;
-    }
-  }
-  // the window after k - 1 rotations with the k-th pending:
-  // lane fl holds U_{k-1}, then U_k..U_{m-1} (count c), then
-  // U_{k-2}..U_0 (count c + 1, each placed in front of the last)
-  const uint32_t rel = lane - fl;
-  uint32_t src = lane;
-  if (lane >= fl && lane < fl + m) src = fl + (rel == 0 ? k - 1 : (rel <= m - k ? k - 1 + rel : m - 1 - rel));
-  w.ow = (uint32_t)__shfl((int)w.ow, (int)src);
-  w.wsl = shfl_u64(w.wsl, src);
-  w.wrm = shfl_u64(w.wrm, src);
-  w.wtok = (uint32_t)__shfl((int)w.wtok, (int)src);
-  return w;
-}
-
 // The generic sort's one out-of-line body: the members arrive as scalar
 // arguments and the sorter is rebuilt locally, so they stay in registers (a
 // member function would reload them through a `this` pointer in scratch
@@ -965,7 +864,6 @@ __device__ __forceinline__ bool pivot_touched(uint32_t modkind, uint32_t modpos,
 // carries none of the wide rows' lane-split code, and the other way round
 template <uint32_t RR, bool TOPO, bool CH = false, bool WIDE = false>
 __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
-  constexpr bool KNOWN_PART = GS_KNOWN_PARTITION == 1 || (GS_KNOWN_PARTITION == 2 && TOPO);
   extern __shared__ uint64_t lds64[];
   __shared__ Frame s_stk[64];
 #ifdef GS_SORT_TL
@@ -1047,11 +945,9 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
   if (wave == 1) {
     // ================================================== memory agent wave
     // (1) stages the next first-pass pod records (queue order) into the LDS
-    //     ring ahead of the solver; (2) with GS_AGENT_WRITES=1 only (the
-    //     round-2 design), performs the solver's posted global writes (add
-    //     log, fast-accept request totals) and reports their completion; by
-    //     default the solver issues them itself (fire-and-forget) and only
-    //     the final WQ_STOP is posted.
+    //     ring ahead of the solver; (2) serves the write queue, which carries
+    //     only the final WQ_STOP: the solver issues its global writes itself
+    //     (the agent performing them was round 2's design).
     const uint32_t* qv_dw = (const uint32_t*)d.qvars;
     const uint32_t* qr_dw = (const uint32_t*)d.qreqs;
     uint32_t k_fill = 0, head = 0, idle = 0, beat = 0;
@@ -1118,11 +1014,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
         idle = 0;
         beat = hb;
       } else {
-#ifdef GS_AGENT_SLEEP
-        __builtin_amdgcn_s_sleep(GS_AGENT_SLEEP);
-#else
         __builtin_amdgcn_s_sleep(1);
-#endif
         if (++idle > SPIN_MAX) break;
       }
     }
@@ -1188,17 +1080,13 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
     }
   };
 
-  // Solver-side global writes (GS_AGENT_WRITES=0, the default): the add log
-  // entry (lane 0) and, for a requests-only Add, the no-return atomic adds
-  // of the requests (lanes r < min(R, 4)).  They are fire-and-forget: the
-  // next exact check's loads wait on the vector memory counter, which the
-  // wave's earlier stores and atomics precede, instead of draining the
-  // agent's channel.
-#ifndef GS_AGENT_WRITES
-#define GS_AGENT_WRITES 0
-#endif
+  // Solver-side global writes: the add log entry (lane 0) and, for a
+  // requests-only Add, the no-return atomic adds of the requests (lanes
+  // r < min(R, 4)).  They are fire-and-forget: the next exact check's loads
+  // wait on the vector memory counter, which the wave's earlier stores and
+  // atomics precede.
   auto emit = [&](uint32_t type, uint32_t idx, uint32_t pod, uint32_t var, uint32_t tgt, uint32_t rqd_, int64_t rql) {
-    if (GS_AGENT_WRITES) {
+    if (false) {  // never taken: it only keeps post among the closure's captures until post itself goes
       post(type, idx, pod, var, tgt, rqd_);
       return;
     }
@@ -1218,21 +1106,9 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
   // instrumentation counters, lane k = counter k (no scalar registers)
   enum { C_GEN = 0, C_FAST, C_CAND, C_FULL, C_NEV, C_NPRE, C_FA, C_ALG,
          // run mode (diagnostics, Ctrl.dbg[8..13] outside the timeline build)
-         C_RPODS, C_RENTER, C_RX_PIVOT, C_RX_WIN, C_RX_SPEC, C_RX_SCAN, C_RX_XC, C_RBATCH, C_RBPODS, C_RBT0, C_RBT1 };
+         C_RPODS, C_RENTER, C_RX_PIVOT, C_RX_WIN, C_RX_SPEC, C_RX_SCAN, C_RX_XC, C_RBATCH, C_RBPODS };
   uint64_t ctr = 0;
-#ifdef GS_NO_CTR  // experiment builds: the counters' cost
-#define CTR(k, x) ((void)0)
-#elif defined(GS_CTR_LDS)  // experiment: counters as no-return LDS atomic adds by lane 0
-  __shared__ unsigned long long s_ctr[8];
-  if (lane < 8) s_ctr[lane] = 0;
-  wsync();
-#define CTR(k, x)                                                        \
-  do {                                                                   \
-    if (lane == 0) atomicAdd(&s_ctr[(k)], (unsigned long long)(x));     \
-  } while (0)
-#else
 #define CTR(k, x) (ctr += lane == (k) ? (uint64_t)(x) : 0ull)
-#endif
   const uint64_t max_pops = ((uint64_t)(d.V - d.P) + 2) * (uint64_t)P + P + 16;
 
 #ifdef GS_FFD_TL
@@ -1243,8 +1119,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
   uint64_t n_fsum = 0, n_xns = 0, n_xb = 0, n_xwin = 0, n_nonsimple = 0, n_rot = 0, n_rotlen = 0, n_gen_cyc = 0;
 #endif
   uint32_t pf_x = 0, pf_seq = 0;  // prefetched ring record and its sequence word
-  // Runs of identical simple pods (GS_RUNS).  Queue order puts equal
-  // requests together (cpu, memory descending), so most first-pass pods
+  // Runs of identical simple pods.  Queue order puts equal requests together (cpu, memory descending), so most first-pass pods
   // repeat the previous pod's spec (CM: 88 % of pods, runs of 8 on average).
   // For such a pod the whole NodeClaim.CanAdd chain -- the pending one-claim
   // sort.Slice rotation, the scan from the infeasible-prefix bound, the fast
@@ -1256,32 +1131,8 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
   // keys leaving the window, a candidate needing the exact check, no
   // candidate in the window, another spec) writes the window back and hands
   // the pod to the general path below.
-#ifndef GS_RUNS
-#define GS_RUNS 1
-#endif
-#ifndef GS_RUN_EXACT
-#define GS_RUN_EXACT 1
-#endif
-#ifndef GS_RUN_REBASE
-#define GS_RUN_REBASE 1
-#endif
-#ifndef GS_RUN_NODES
-#define GS_RUN_NODES 1
-#endif
-// GS_RUN_BATCH=1: up to 16 pods of a run placed in one step (round 6,
-// bit-exact).  Off by default: it cuts run-mode cycles per pod 4,225 -> 3,914
-// on CM, but the pod loop's register allocation around the added code costs
-// the general path as much (same session, FFD ms: CM 283.2 -> 282.9, C2
-// 36.4 -> 37.7, C1 3.18 -> 3.51; profiles/r6/run_batch_*.txt)
-#ifndef GS_RUN_BATCH
-#define GS_RUN_BATCH 0
-#endif
-#ifndef GS_RUN_WIDE  // the wide-row instantiation in run mode
-#define GS_RUN_WIDE 0
-#endif
-#ifndef GS_RUN_WIDE_EXACT  // ... with the window's exact checks, one candidate at a time over all lanes
-#define GS_RUN_WIDE_EXACT 1
-#endif
+  // (Placing up to 16 pods of a run in one step was tried and cost the general
+  // path what it saved: DESIGN.md, profiles/r6/run_batch_*.txt.)
 #ifdef GS_RUN_TL
   uint64_t run_cyc = 0;  // s_memtime ticks inside run mode
 #endif
@@ -1331,8 +1182,8 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
     // (existing nodes: only once the run's spec is known to fit none of them --
     // its last general pod, a plain pod, set the node hint past the last node;
     // nodes only fill up and no run pod is placed on one)
-    if (GS_RUNS && !TOPO && (!WIDE || GS_RUN_WIDE) && run_prev && !wrapped && modkind == MOD_INC && M >= 50 &&
-        (d.NN == 0 || (GS_RUN_NODES && nhint_ok && nhint >= d.NN))) {
+    if (!TOPO && !WIDE && run_prev && !wrapped && modkind == MOD_INC && M >= 50 &&
+        (d.NN == 0 || (nhint_ok && nhint >= d.NN))) {
       run_prev = false;
       auto same_spec = [&](uint32_t x) {
         return __ballot(lane >= 1 && lane < RING_QRUN && lane != VR_DW - 1 && x != run_rec) == 0;
@@ -1384,14 +1235,13 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
           const uint32_t eo = b ? ffs64(b) : 64u;
           if (!b) {
             // a pivot sample touched, or the raised claim's run of equal keys
-            // leaves the window (GS_RUN_REBASE): the window goes back to LDS,
+            // leaves the window: the window goes back to LDS,
             // the general path's sort step runs there (one rotation past the
             // run; with a touched sample only when choosePivot still reports
             // "increasing", else the pod leaves for the general sort), and
             // the window is re-read at the infeasible-prefix bound (modpos:
             // the claims after it moved one position left)
             CTR(ptouch ? C_RX_PIVOT : C_RX_WIN, 1);
-            if (!GS_RUN_REBASE) break;
             wsyncT<CH>();
             if (dirty && valid) {
               s_so[wpos] = ow;
@@ -1440,7 +1290,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             break;
           }
           uint32_t fl = ffs64(lpb);
-          // The exact NodeClaim.CanAdd inside the run (GS_RUN_EXACT): the
+          // The exact NodeClaim.CanAdd inside the run: the
           // window's candidates before its first fast accept that need it (a
           // threshold cursor would move) are checked one lane each, as the
           // general path's phase B checks the same batch; the first feasible
@@ -1448,7 +1298,6 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
           // leaves the run (the general path scans on past it)
           bool xwin = false;
           uint64_t x_nx[WREG] = {0, 0, 0, 0};
-          uint64_t x_w[2] = {0, 0};  // wide rows: this lane's option words (lane, lane + 64) after the Add
           int64_t x_tot[RR], x_ma[RR];
           uint32_t x_mrow[RR];
           uint64_t x_zm = 0;
@@ -1464,7 +1313,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             return (int64_t)((uint64_t)rlane(run_rec, 32 + 2 * r) | ((uint64_t)rlane(run_rec, 33 + 2 * r) << 32));
           };
           if (!(fab & 1ull << fl)) {
-            if (!GS_RUN_EXACT || (WIDE && !GS_RUN_WIDE_EXACT) || rlane(run_rec, 2) != 0) {  // free-key entries: the general path
+            if (rlane(run_rec, 2) != 0) {  // free-key entries: the general path
               CTR(C_RX_SCAN, 1);
               break;
             }
@@ -1473,71 +1322,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             const auto& KD = *karg();
             const uint32_t pvx = rlane(pf_x, VR_DW - 1);  // the next pod's variant (its K1 rows)
             bool feas = false;
-            uint64_t fm = 0;
-            if (WIDE) {
-              // wide rows: the candidates one after another in window order,
-              // every lane one option word (and the word 64 on); the first
-              // feasible one wins, as in the general path's batch
-              for (uint64_t exw = ex; exw; exw &= exw - 1) {
-                const uint32_t c = ffs64(exw);
-                const uint32_t j = rlane(ow, c) >> 16;
-                const uint32_t t = T > 1 ? (uint32_t)s_tmpl[j] : 0u;
-                const ClaimRec* cr = KD.c_rec + j;
-                uint32_t cur[RR];
-#pragma unroll
-                for (uint32_t r = 0; r < RR; r++) x_ma[r] = cr->maxa[r];
-                uint64_t x_cm;
-                {
-                  const uint4* q = (const uint4*)cr;
-                  const uint4 h0 = q[0], h1 = q[1], h2 = q[2], h3 = q[3];
-                  const int64_t tl4[4] = {(int64_t)(((uint64_t)h0.y << 32) | h0.x), (int64_t)(((uint64_t)h0.w << 32) | h0.z),
-                                          (int64_t)(((uint64_t)h1.y << 32) | h1.x), (int64_t)(((uint64_t)h1.w << 32) | h1.z)};
-                  const uint32_t cl[4] = {h2.x & 0xFFFFu, h2.x >> 16, h2.y & 0xFFFFu, h2.y >> 16};
-                  x_zm = ((uint64_t)h2.w << 32) | h2.z;
-                  x_cm = ((uint64_t)h3.y << 32) | h3.x;
-#pragma unroll
-                  for (uint32_t r = 0; r < RR; r++) {
-                    x_tot[r] = r < 4 ? tl4[r] : cr->tot_hi[r - 4];
-                    cur[r] = r < 4 ? cl[r] : cr->thr_hi[r - 4];
-                  }
-                }
-                const uint64_t G = grid_of(x_zm & vzm, x_cm & vcm, KD.Z, KD.C);
-                const uint64_t Gt = grid_of(s_tzm[t] & vzm, s_tcm[t] & vcm, KD.Z, KD.C);
-                uint32_t mm[RR];
-#pragma unroll
-                for (uint32_t r = 0; r < RR; r++) {
-                  const uint32_t o = s_thoff[r], n = s_thoff[r + 1] - o;
-                  mm[r] = thr_window(thr + o, n, cur[r], x_tot[r] + RQV(r));
-                  if (mm[r] == cur[r] + 4 && mm[r] < n) mm[r] = thr_search(thr + o, n, mm[r], x_tot[r] + RQV(r));
-                  x_mrow[r] = o + r + mm[r];
-                }
-                const uint64_t* row = KD.rows + ((size_t)pvx * T + t) * OW;
-                const uint64_t* opts = KD.c_opts + (size_t)j * OW;
-                bool anyw = false;
-#pragma unroll
-                for (uint32_t h = 0; h < 2; h++) {
-                  const uint32_t w = lane + 64 * h;
-                  uint64_t x = 0;
-                  if (w < W) {
-                    x = opts[w] & row[w];
-#pragma unroll
-                    for (uint32_t r = 0; r < RR; r++)
-                      if (mm[r] != cur[r]) x &= KD.thr_set[(size_t)x_mrow[r] * OW + w];
-                    if (G != Gt) {
-                      uint64_t off = 0;
-                      for (uint64_t gm = G; gm; gm &= gm - 1) off |= slot[(size_t)ffs64(gm) * W + w];
-                      x &= off;
-                    }
-                  }
-                  x_w[h] = x;
-                  anyw = anyw || x != 0;
-                }
-                if (__ballot(anyw)) {
-                  fm = 1ull << c;
-                  break;
-                }
-              }
-            } else if ((ex >> lane) & 1) {
+            if ((ex >> lane) & 1) {
               const uint32_t j = ow >> 16;
               const uint32_t t = T > 1 ? (uint32_t)s_tmpl[j] : 0u;
               const ClaimRec* cr = KD.c_rec + j;
@@ -1615,7 +1400,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             }
             CTR(C_FULL, __popcll(ex));
             CTR(C_RX_XC, 1);
-            if (!WIDE) fm = __ballot(feas);
+            const uint64_t fm = __ballot(feas);
             if (fm) {
               fl = ffs64(fm);
               xwin = true;
@@ -1648,22 +1433,13 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             // slack / room codes, requirements; the window takes the codes
             const auto& KD = *karg();
             const uint32_t vctb = rlane(run_rec, 3);
-            if (WIDE) {
-              // the winner's option words, one lane per word
-              uint64_t* wopts = KD.c_opts + (size_t)(e >> 16) * OW;
-#pragma unroll
-              for (uint32_t h = 0; h < 2; h++)
-                if (lane + 64 * h < W) wopts[lane + 64 * h] = x_w[h];
-            }
             if (lane == fl) {
               const uint32_t j = ow >> 16;
               ClaimRec* cr = KD.c_rec + j;
               uint64_t* opts = KD.c_opts + (size_t)j * OW;
-              if (!WIDE) {
 #pragma unroll
-                for (uint32_t w = 0; w < WREG; w++)
-                  if (w < W) opts[w] = x_nx[w];
-              }
+              for (uint32_t w = 0; w < WREG; w++)
+                if (w < W) opts[w] = x_nx[w];
               int64_t nt[RR];
               uint32_t cu[RR];
 #pragma unroll
@@ -1739,88 +1515,6 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
           modkind = MOD_INC;
           modpos = f;
           lf = fl;
-#if GS_RUN_BATCH
-          // A batch of the run's next pods.  This pod
-          // joined U_0, the claim at lane fl (count c -> c + 1); U_1.. at
-          // lanes fl + 1.. are the other count-c claims (up to lane e2).
-          // sort.Slice moves U_0 behind them, so the next pod's scan (from
-          // position f: the prefix before it stays infeasible) finds U_1 at f;
-          // if U_1 is a fast accept (its bit in this scan's fab) the pod joins
-          // it, its sort.Slice is the same one rotation from the same position
-          // f (one choosePivot check for all), and so on: pod j joins U_j.
-          // While U_j is a fast accept and the ring holds the next record of
-          // the run's spec (qrun), up to 16 pods are placed here at once --
-          // log entries and request atomics lane-parallel, U_j's codes
-          // re-quantized on its own lane, the window permuted once -- and the
-          // last pod's rotation stays pending as after a single Add.
-          // Bit-identical to placing them one by one.
-          {
-#ifdef GS_RUN_TL
-            const uint64_t tb0 = __builtin_amdgcn_s_memtime();
-#endif
-            const uint32_t c = e & 0xFFFFu;
-            const uint64_t after = __ballot(lane > fl && (ow & 0xFFFFu) > c);
-            uint32_t k = 1;
-            if (after && c + 2u < 0xFFFFu && !pivot_touched(MOD_INC, f, M)) {
-              const uint32_t m = ffs64(after) - fl;  // U_0..U_{m-1} at lanes fl..fl + m - 1
-              k = 1u + (uint32_t)__builtin_ctzll(~(fab >> (fl + 1)));
-              k = k < m ? k : m;
-              const uint32_t nrun = rlane(x_rec, RING_QRUN);
-              k = k < nrun ? k : nrun;
-              const uint32_t q1 = qhead - 1;  // this pod's queue position
-              if (q1 + k > P - 1) k = P - 1 - q1;
-              if (pops + k > max_pops) k = 1;
-              if (k >= 2) {
-                // pods 2..k (lanes j = 1..k-1, queue position q1 + j): the
-                // sequence word, pod and variant in one LDS round trip
-                const bool jl = lane >= 1 && lane < k;
-                const uint32_t slot = (q1 + lane) % RING;
-                const uint32_t sq = jl ? vld(&s_ring_seq[slot]) : 0u;
-                const uint32_t bp = jl ? vld(&s_ring[slot][0]) : 0u;
-                const uint32_t bv = jl ? vld(&s_ring[slot][VR_DW - 1]) : 0u;
-                k = 1u + (uint32_t)__builtin_ctzll(~(__ballot(jl && sq == q1 + lane + 1) >> 1));
-#ifdef GS_RUN_TL
-                const uint64_t tb1 = __builtin_amdgcn_s_memtime();
-#endif
-                if (k >= 2) {
-                  const auto& KD = *karg();
-                  RunWin rw{ow, wtok, wsl, wrm};
-                  rw = run_batch_place<RR>(rw, (uint64_t)r_rq, bp, bv, fl, m, k, nlog, d.RQ, KD.log, KD.c_rec);
-                  ow = rw.ow;
-                  wtok = rw.wtok;
-                  wsl = rw.wsl;
-                  wrm = rw.wrm;
-                  // Queue.Pop of pods 2..k: their ring slots may be refilled
-                  wsyncT<CH>();
-                  if (lane == 0) {
-                    vst(&s_ctl[0], q1 + k);
-                    vst(&s_ctl[3], (uint32_t)(pops + k - 1));
-                  }
-                  qhead = q1 + k;
-                  qlen -= k - 1;
-                  pops += k - 1;
-                  nlog += k - 1;
-                  pf_seq = vld(&s_ring_seq[qhead % RING]);
-                  pf_x = lane < RING_DW ? vld(&s_ring[qhead % RING][lane]) : 0u;
-                  CTR(C_FAST, k - 1);
-                  CTR(C_CAND, (uint64_t)(k - 1) * (M - f < 64 ? M - f : 64));
-                  CTR(C_FA, k - 1);
-                  CTR(C_ALG, (uint64_t)(k - 1) * (f + 1));
-                  CTR(C_NPRE, (uint64_t)(k - 1) * d.NN);
-                  CTR(C_RPODS, k - 1);
-                  CTR(C_RBATCH, 1);
-                  CTR(C_RBPODS, k - 1);
-#ifdef GS_RUN_TL
-                  CTR(C_RBT1, __builtin_amdgcn_s_memtime() - tb1);
-#endif
-                }
-              }
-            }
-#ifdef GS_RUN_TL
-            CTR(C_RBT0, __builtin_amdgcn_s_memtime() - tb0);
-#endif
-          }
-#endif
         }
         if (dirty) {
           // the window back to LDS: positions, and the codes of its claims
@@ -2010,7 +1704,6 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
         const bool need = lp & !fa & (lane < mfl);
         bool feas = fa;
         if (__ballot(need)) {
-          if (GS_AGENT_WRITES) drain();  // node requests the agent still adds (fast accepts)
           if (need) {
             const NodeRec& nr = KD.nodes[n];
             const FK* nfk = KD.n_fk + (size_t)n * F;
@@ -2196,12 +1889,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
       inversion = __builtin_amdgcn_readfirstlane(inversion ? 1u : 0u) != 0;
       if (inversion) {
         if (M <= 12) {
-          if (GS_REG_SORT) {
-            reg_pdq_frame(PackedArr<U32, CH>{(U32*)s_so}, 0, (int)M, bits_len((uint64_t)M), 1, 1);  // insertionSort
-          } else {
-            if (lane == 0) SeqSortT<PackedAccT<U32>>{{(U32*)s_so}}.insertion_sort(0, (int)M);
-            wsyncT<CH>();
-          }
+          reg_pdq_frame(PackedArr<U32, CH>{(U32*)s_so}, 0, (int)M, bits_len((uint64_t)M), 1, 1);  // insertionSort
           hint_ok = false;
         } else if (M >= 50 && (!pivot_touched(modkind, modpos, M) || pivot_hint_wave(acc, (int)M, lane) == 1)) {
           // partialInsertionSort fixes the single inversion: one rotation
@@ -2234,9 +1922,9 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
           const uint64_t g0_ = __builtin_amdgcn_s_memtime();
 #endif
 #ifdef GS_SORT_TL
-          wave_pdqsort<GS_WAVE_SEQ, U32, U16, CH, KNOWN_PART>(ws.so, ws.scr, ws.stk, ws.lane, ws.half, (int)M, known_x, s_stl);
+          wave_pdqsort<GS_WAVE_SEQ, U32, U16, CH, true>(ws.so, ws.scr, ws.stk, ws.lane, ws.half, (int)M, known_x, s_stl);
 #else
-          wave_pdqsort<GS_WAVE_SEQ, U32, U16, CH, KNOWN_PART>(ws.so, ws.scr, ws.stk, ws.lane, ws.half, (int)M, known_x);
+          wave_pdqsort<GS_WAVE_SEQ, U32, U16, CH, true>(ws.so, ws.scr, ws.stk, ws.lane, ws.half, (int)M, known_x);
 #endif
 #ifdef GS_FFD_TL
           n_gen_cyc += __builtin_amdgcn_s_memtime() - g0_;
@@ -2251,21 +1939,14 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
     // rqq_p / rqc_p: the request codes for the LDS slack / room tests, packed
     // 16 bits per resource (codes < 2^15, so a SWAR subtract compares all four
     // at once)
-#ifdef GS_NO_FAST
-    bool simple = false;
-#else
     // a pod with no requirements and no owned topology group (VF_SIMPLE):
     // its CanAdd is resources and taints only, in either variant
     bool simple = (vctb & VF_SIMPLE) != 0;
-#endif
     simple = simple && !rq_hi;  // room covers resources 0..3
     // hostname-only topology (VF_HOSTFA): the scan reads each candidate's
     // counts of the owned groups; a candidate over a skew is infeasible
     // (dropped), one within them that passes the room test is a fast accept
-#ifndef GS_HOSTFA
-#define GS_HOSTFA 1
-#endif
-    const bool hostfa = GS_HOSTFA && TOPO && !rq_hi && (vctb & VF_HOSTFA) != 0;
+    const bool hostfa = TOPO && !rq_hi && (vctb & VF_HOSTFA) != 0;
 #ifdef GS_FFD_TL
     n_nonsimple += simple ? 0u : 1u;
 #endif
@@ -2300,10 +1981,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
       // 322); the general narrow variant measured no better (e2e, C3) and
       // keeps the plain loop; gathering the next chunk's codes too measured
       // slower (C5 1,245 -> 1,270; profiles/r4/scan_prefetch_ab.txt)
-#ifndef GS_SCAN_PF
-#define GS_SCAN_PF 1
-#endif
-      constexpr bool SPF = GS_SCAN_PF && (WIDE || !TOPO);
+      constexpr bool SPF = WIDE || !TOPO;
       uint32_t ev_next = 0;
       bool have_next = false;
       for (uint32_t cb = scan_from; cb < M; cb += 64) {
@@ -2323,20 +2001,10 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
         if (TOPO && hostfa && lp) {
           const auto& KD = *karg();
           const int32_t* hrow = KD.hc + (size_t)je * KD.TGH;
-#ifdef GS_HOSTFA_UNROLL
-#pragma unroll
-          for (uint32_t k = 0; k < 4; k++) {
-            if (k < own_n) {
-              const int64_t c = hrow[rlane(og_slot, k)] + ((rlane(og_e, k) & TL_SELF) ? 1 : 0);
-              lp = lp && c <= (int64_t)(int32_t)rlane(og_skew, k);
-            }
-          }
-#else
           for (uint32_t k = 0; k < own_n; k++) {
             const int64_t c = hrow[rlane(og_slot, k)] + ((rlane(og_e, k) & TL_SELF) ? 1 : 0);
             lp = lp && c <= (int64_t)(int32_t)rlane(og_skew, k);
           }
-#endif
         }
         const bool fa = lp & (simple | hostfa) & swar_ge(rmv, rqc_p);
         const uint64_t fab = __ballot(fa), exb = __ballot(lp & !fa);
@@ -2365,7 +2033,6 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
       wsyncT<CH>();
       TLW(5);  // phase A: LDS prefilter
       if (nex) {
-        if (GS_AGENT_WRITES) drain();  // the agent's request totals must be in the claim records
         const auto& KD = *karg();
         const uint32_t vx = fresh(vrd);
         auto VX = [&](uint32_t i) -> uint32_t { return rlane(vx, i); };
@@ -2383,11 +2050,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
         // wide option rows (W > WREG words): a small batch spreads each
         // candidate over L lanes, each testing every L-th 4-word chunk, so a
         // candidate takes W / 4L dependent round trips instead of W / 4
-#ifdef GS_NO_EXACT_LANES  // experiment builds: one lane per candidate at every width
-        const uint32_t lgL = 0u;
-#else
         const uint32_t lgL = !WIDE ? 0u : nex <= 8 ? 3u : nex <= 16 ? 2u : nex <= 32 ? 1u : 0u;
-#endif
         const uint32_t lgW = W <= 4 ? 0u : W <= 8 ? 1u : W <= 16 ? 2u : 3u;  // no more lanes than 4-word chunks
         const uint32_t lg = lgL < lgW ? lgL : lgW;
         const uint32_t cx = lane >> lg, sub = lane & ((1u << lg) - 1u);
@@ -2401,12 +2064,9 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
       uint32_t czfl = 0;
       uint32_t mrow[RR];
       int64_t tot[RR];
-      // GS_MAXA_PF: each candidate lane also loads its claim's maxa (the
-      // slack bound the Add re-quantizes with) with the header, so the
-      // winner's Add does not wait on a load of its own
-#ifndef GS_MAXA_PF
-#define GS_MAXA_PF 1
-#endif
+      // each candidate lane also loads its claim's maxa (the slack bound the
+      // Add re-quantizes with) with the header, so the winner's Add does not
+      // wait on a load of its own
       int64_t maxa_pre[RR];
 #pragma unroll
       for (uint32_t r = 0; r < RR; r++) maxa_pre[r] = 0;
@@ -2415,10 +2075,8 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
       if (cx < nex) {
         const ClaimRec* cr = KD.c_rec + j;
         uint32_t cur[RR];
-        if (GS_MAXA_PF) {
 #pragma unroll
-          for (uint32_t r = 0; r < RR; r++) maxa_pre[r] = cr->maxa[r];
-        }
+        for (uint32_t r = 0; r < RR; r++) maxa_pre[r] = cr->maxa[r];
         {
           const uint4* q = (const uint4*)cr;
           const uint4 h0 = q[0], h1 = q[1], h2 = q[2], h3 = q[3];
@@ -2590,7 +2248,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
 #ifdef GS_FFD_TL
           n_xwin++;
 #endif
-        if (GS_ADD_LANES && WIDE) {
+        if (WIDE) {
           // the winner's option words after Add, one lane per word (one
           // round trip per 64 words instead of one per word): its threshold
           // rows and offering grid come from its lane
@@ -2623,26 +2281,13 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
   #pragma unroll
             for (uint32_t w = 0; w < WREG; w++)
               if (w < W) opts[w] = nx[w];  // already narrowed to the grid
-          } else if (WIDE && !GS_ADD_LANES) {
-            const uint64_t* row = KD.rows + ((size_t)v * T + t) * OW;
-            for (uint32_t w = 0; w < W; w++) {
-              uint64_t x = opts[w] & row[w];
-  #pragma unroll
-              for (uint32_t r = 0; r < RR; r++) x &= KD.thr_set[(size_t)mrow[r] * OW + w];
-              if (G != Gt) {
-                uint64_t off = 0;
-                for (uint64_t gm = G; gm; gm &= gm - 1) off |= slot[(size_t)ffs64(gm) * W + w];
-                x &= off;
-              }
-              opts[w] = x;
-            }
           }
           int64_t nt[RR], ma[RR];
           uint32_t cu[RR];
   #pragma unroll
           for (uint32_t r = 0; r < RR; r++) {
             nt[r] = tot[r] + RQ(r);
-            ma[r] = GS_MAXA_PF ? maxa_pre[r] : cr->maxa[r];
+            ma[r] = maxa_pre[r];
             cu[r] = mrow[r] - s_thoff[r] - r;
             cr->tot(r) = nt[r];
             cr->thr(r) = (uint16_t)cu[r];
@@ -2754,7 +2399,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
       modpos = f;
       nlog++;
       // the next pod may repeat this one's spec (runs, above)
-      run_prev = GS_RUNS && !TOPO && (!WIDE || GS_RUN_WIDE) && from_ring && simple && !__ballot(ovf);
+      run_prev = !TOPO && !WIDE && from_ring && simple && !__ballot(ovf);
       CAT(simple ? 1 : 3);
       run_rec = vrd;
       continue;
@@ -2983,12 +2628,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
     d.c_sorted[i] = e >> 16;
     d.c_rec[e >> 16].count = e & 0xFFFFu;
   }
-#ifdef GS_CTR_LDS
-  wsync();
-  auto ctr_at = [&](uint32_t k) -> uint64_t { return (uint64_t)s_ctr[k]; };
-#else
   auto ctr_at = [&](uint32_t k) -> uint64_t { return (uint64_t)rlane((uint32_t)ctr, k) | ((uint64_t)rlane((uint32_t)(ctr >> 32), k) << 32); };
-#endif
   const uint64_t ctr_gen = ctr_at(C_GEN), ctr_fast = ctr_at(C_FAST), ctr_cand = ctr_at(C_CAND), ctr_full = ctr_at(C_FULL),
                  ctr_nev = ctr_at(C_NEV), ctr_npre = ctr_at(C_NPRE), ctr_fa = ctr_at(C_FA), ctr_alg = ctr_at(C_ALG);
 #ifdef GS_CAT_TL
@@ -3031,12 +2671,8 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
 #else
     c.dbg[14] = ctr_run[6];  // run-mode exact batches
 #endif
-    c.dbg[5] = ctr_at(C_RBPODS);  // pods placed in run batches (GS_RUN_BATCH)
-    c.dbg[6] = ctr_at(C_RBATCH);  // run batches
-#ifdef GS_RUN_TL
-    c.dbg[3] = ctr_at(C_RBT0);  // ticks in the batch step, check included
-    c.dbg[4] = ctr_at(C_RBT1);  // ticks in the batches' placement
-#endif
+    c.dbg[5] = ctr_at(C_RBPODS);  // the removed run batches' counters: always 0
+    c.dbg[6] = ctr_at(C_RBATCH);
 #endif
     c.t_sort = c.t_scan = c.t_tmpl = ~0ull;  // not measured: gs_result reports -1
 #ifdef GS_FFD_TL

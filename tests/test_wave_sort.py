@@ -55,9 +55,8 @@ def wave_perm_known(keys, x):
 
 
 def check(keys, x=None):
-    """x: the one position out of order (the Solve's one-change sorts: in a
-    GS_KNOWN_PARTITION=1 build the first partition then searches the
-    boundary, WaveSort::partition_known; the default build ignores x)"""
+    """x: the one position out of order (the Solve's one-change sorts: the
+    first partition then searches the boundary, WaveSort::partition_known)"""
     keys = [int(v) for v in keys]
     want = go_perm(keys)
     assert wave_perm(keys) == want, keys if len(keys) < 80 else len(keys)
