@@ -472,6 +472,32 @@ typedef struct gs_consolidation_result {
 gs_status gs_consolidate(gs_ctx* ctx, const gs_consolidation* in, gs_consolidation_result* out);
 /* re-run the device part on the same input (bench: inputs stay resident) */
 gs_status gs_consolidate_rerun(gs_ctx* ctx, gs_consolidation_result* out);
+/* scheduling.Results of one simulation of the last gs_consolidate /
+ * gs_consolidate_rerun on this context (<U> SimulateScheduling's return value):
+ * `sim` indexes gs_consolidation_result.commands.  The simulation runs again
+ * on the resident input (nothing is encoded or uploaded) and keeps what the
+ * sweep drops: where every pod went.
+ *  - pod indices: i < cluster->n_pods is pending pod i, otherwise
+ *    cluster->n_pods + b for cluster->bound_pods[b];
+ *  - node indices are the cluster's, n_nodes = cluster->n_nodes (a
+ *    candidate's range is empty);
+ *  - claim_pods / node_pods in add order, error_pods ascending; the claim
+ *    fields and the minValues truncation are gs_fetch's (a dropped NodeClaim
+ *    is absent, its pods are error pods);
+ *  - pops is this simulation's; t_ffd_ms, t_truncate_ms, t_fetch_ms and
+ *    t_total_ms describe this call; the other instrumentation fields are 0,
+ *    or -1 where gs_fetch reports "not measured".
+ * For a Replace command, claim 0 is Command.Replacements[0]: its
+ * requirements, resource requests and pods (claim_its is the OrderByPrice
+ * list before the command's price filter; the command's options are a
+ * subsequence of it).
+ * GS_E_INVALID: no consolidation resident, sim >= n_commands, or the command
+ * is GS_DECISION_SKIPPED.  `out` is owned by the context until the next call
+ * that fills a gs_result or a new gs_consolidate; the commands / options of
+ * the consolidation result stay valid, and a following gs_consolidate_rerun
+ * returns the same commands.  A context with shards routes the call to the
+ * shard that evaluated `sim`. */
+gs_status gs_consolidation_results(gs_ctx* ctx, uint32_t sim, gs_result* out);
 /* host-only policy replay over a complete command table (e.g. after an
  * all-gather of sharded evaluations): SINGLE = first non-NoOp in order,
  * MULTI = firstNConsolidationOption's binary search with filterOutSameInstanceType.

@@ -244,6 +244,11 @@ void upload_problem(gs_ctx* c, const SimPlan* sims) {
     pinned(c->h_hdr, NS);
     pinned(c->h_its, NS * 60);
     pinned(c->h_nits, NS);
+    // gs_consolidation_results re-runs one simulation and truncates every
+    // NodeClaim it opened (at most one per pod)
+    c->alloc(c->res_its, (size_t)d.max_claims * 60);
+    c->alloc(c->res_nits, d.max_claims);
+    c->alloc(c->res_drop, d.max_claims);
   }
   c->commit();
   if (!sims) {
@@ -410,6 +415,111 @@ gs_status prepare_from(gs_ctx* c, const gs_ctx* src) {
     return fail(c, GS_E_HIP, e.msg);
   }
   c->prepared = true;
+  return GS_OK;
+}
+
+// A Solve's device records -> the structural fields of a gs_result in the
+// context's result storage (gs_fetch; gs_consolidation_results for one
+// simulation).  The instrumentation fields are the caller's.
+gs_status decode_result(gs_ctx* c, const SolveRecords& r, gs_result* out) {
+  auto& e = c->enc;
+  const uint32_t M = r.n_claims;
+  const gsd::ClaimRec* hdr = r.hdr;
+  const uint32_t* its = r.its;
+  const uint32_t* nits = r.nits;
+  auto pod_of = [&](uint32_t p) { return r.pod_index ? r.pod_index[p] : p; };
+  // pods per claim in add order, and each claim's requirement set
+  std::vector<std::vector<uint32_t>> cp(M);
+  std::vector<gsh::Reqs> creq(M);
+  for (uint32_t j = 0; j < M; j++) creq[j] = e.tmpl_reqs[hdr[j].tmpl];
+  c->node_pod_offsets.assign(1, 0);
+  c->node_pods.clear();
+  std::vector<std::vector<uint32_t>> np_(e.NN);
+  for (uint32_t i = 0; i < r.n_log; i++) {
+    const gsd::LogRec& l = r.log[i];
+    if (l.target & 0x80000000u) {
+      const uint32_t pos = l.target & 0x7FFFFFFFu;
+      if (pos >= e.NN) return fail(c, GS_E_HIP, "corrupt add log");
+      np_[r.node_index[pos]].push_back(pod_of(l.pod));
+      continue;
+    }
+    if (l.target >= M) return fail(c, GS_E_HIP, "corrupt add log");
+    cp[l.target].push_back(pod_of(l.pod));
+    for (auto& kv : e.variants[e.var_sv[l.var]].reqs) gsh::reqs_add(e, creq[l.target], kv.first, kv.second);
+  }
+  c->claim_nodepool.assign(M, 0);
+  c->claim_pod_offsets.assign(1, 0);
+  c->claim_pods.clear();
+  c->claim_it_offsets.assign(1, 0);
+  c->claim_its.clear();
+  c->req_text.assign(M, "");
+  c->claim_requests.assign((size_t)M * e.R, 0);
+  // <U> Results.TruncateInstanceTypes: a NodeClaim whose top 60 by price miss
+  // its template's minValues is dropped, its pods become pod errors
+  std::vector<uint32_t> dropped_pods;
+  uint32_t kept = 0;
+  for (uint32_t j = 0; j < M; j++) {
+    const gsd::TmplRec& tr = e.tmpl[hdr[j].tmpl];
+    bool drop = false;
+    for (uint32_t mm = tr.mv_mask; mm && !drop; mm &= mm - 1) {
+      const uint32_t k = (uint32_t)__builtin_ctz(mm);
+      std::set<uint32_t> vals;
+      for (uint32_t q = 0; q < nits[j]; q++) vals.insert(e.it_vid[(size_t)k * e.N + its[(size_t)j * 60 + q]]);
+      drop = vals.size() < tr.mv[k];
+    }
+    if (drop) {
+      dropped_pods.insert(dropped_pods.end(), cp[j].begin(), cp[j].end());
+      continue;
+    }
+    c->claim_nodepool[kept] = tr.np_index;
+    c->claim_pods.insert(c->claim_pods.end(), cp[j].begin(), cp[j].end());
+    c->claim_pod_offsets.push_back((uint32_t)c->claim_pods.size());
+    c->claim_its.insert(c->claim_its.end(), its + (size_t)j * 60, its + (size_t)j * 60 + nits[j]);
+    c->claim_it_offsets.push_back((uint32_t)c->claim_its.size());
+    if (e.TG && e.keys[e.k_dom].vocab.size() <= (size_t)gsd::ZVMAX && !(hdr[j].zflags & gsd::ZF_COMP)) {
+      // topology spread narrowed the zone to In[domain]: the device's zone
+      // Has already includes it (template AND pods AND topology)
+      gsh::KReq q;
+      q.comp = false;
+      q.has = gsh::Bits(e.keys[e.k_dom].vocab.words());
+      q.excl = gsh::Bits(e.keys[e.k_dom].vocab.words());
+      q.has.w[0] = hdr[j].zfull;
+      gsh::reqs_add(e, creq[j], e.k_dom, q);
+    }
+    creq[j].erase(e.k_hostname);  // FinalizeScheduling
+    c->req_text[kept] = gsh::canonical(e, creq[j]);
+    for (uint32_t x = 0; x < e.R; x++) c->claim_requests[(size_t)kept * e.R + x] = hdr[j].tot(x);
+    kept++;
+  }
+  c->claim_nodepool.resize(kept);
+  c->req_text.resize(kept);
+  c->claim_requests.resize((size_t)kept * e.R);
+  c->req_ptrs.clear();
+  for (auto& s : c->req_text) c->req_ptrs.push_back(s.c_str());
+  c->error_pods.clear();
+  for (uint32_t i = 0; i < r.n_unplaced; i++) c->error_pods.push_back(pod_of(r.unplaced[i]));
+  c->error_pods.insert(c->error_pods.end(), dropped_pods.begin(), dropped_pods.end());
+  std::sort(c->error_pods.begin(), c->error_pods.end());
+  for (auto& v : np_) {
+    c->node_pods.insert(c->node_pods.end(), v.begin(), v.end());
+    c->node_pod_offsets.push_back((uint32_t)c->node_pods.size());
+  }
+  std::memset(out, 0, sizeof(*out));
+  out->n_claims = kept;
+  out->claim_nodepool = c->claim_nodepool.data();
+  out->claim_pod_offsets = c->claim_pod_offsets.data();
+  out->claim_pods = c->claim_pods.data();
+  out->claim_it_offsets = c->claim_it_offsets.data();
+  out->claim_its = c->claim_its.data();
+  out->claim_requirements = c->req_ptrs.data();
+  out->n_resources = e.R;
+  out->resource_names = e.res_name_ids.data();
+  out->claim_requests = c->claim_requests.data();
+  out->n_nodes = e.NN;
+  out->node_pod_offsets = c->node_pod_offsets.data();
+  out->node_pods = c->node_pods.data();
+  out->n_errors = (uint32_t)c->error_pods.size();
+  out->error_pods = c->error_pods.data();
   return GS_OK;
 }
 
@@ -686,99 +796,13 @@ gs_status gs_fetch(gs_ctx* c, gs_result* out) {
     return fail(c, GS_E_CAPACITY, "a NodeClaim would hold more than 65535 pods (16-bit pod count in LDS)");
   if (c->ctrl.status == gsd::ST_INTERNAL) return fail(c, GS_E_HIP, "ffd kernel reported an internal error (queue / channel bound)");
   if (c->ctrl.status != 0) return fail(c, GS_E_HIP, "ffd kernel reported an unknown status");
-  const uint32_t M = c->ctrl.n_claims;
-  // pods per claim in add order, and each claim's requirement set
-  std::vector<std::vector<uint32_t>> cp(M);
-  std::vector<gsh::Reqs> creq(M);
-  for (uint32_t j = 0; j < M; j++) creq[j] = e.tmpl_reqs[hdr[j].tmpl];
-  c->node_pod_offsets.assign(1, 0);
-  c->node_pods.clear();
-  std::vector<std::vector<uint32_t>> np_(e.NN);
-  for (auto& l : log) {
-    if (l.target & 0x80000000u) {
-      const uint32_t pos = l.target & 0x7FFFFFFFu;
-      if (pos >= e.NN) return fail(c, GS_E_HIP, "corrupt add log");
-      np_[e.node_order[pos]].push_back(l.pod);
-      continue;
-    }
-    if (l.target >= M) return fail(c, GS_E_HIP, "corrupt add log");
-    cp[l.target].push_back(l.pod);
-    for (auto& kv : e.variants[e.var_sv[l.var]].reqs) gsh::reqs_add(e, creq[l.target], kv.first, kv.second);
-  }
-  c->claim_nodepool.assign(M, 0);
-  c->claim_pod_offsets.assign(1, 0);
-  c->claim_pods.clear();
-  c->claim_it_offsets.assign(1, 0);
-  c->claim_its.clear();
-  c->req_text.assign(M, "");
-  c->claim_requests.assign((size_t)M * e.R, 0);
-  // <U> Results.TruncateInstanceTypes: a NodeClaim whose top 60 by price miss
-  // its template's minValues is dropped, its pods become pod errors
-  std::vector<uint32_t> dropped_pods;
-  uint32_t kept = 0;
-  for (uint32_t j = 0; j < M; j++) {
-    const gsd::TmplRec& tr = e.tmpl[hdr[j].tmpl];
-    bool drop = false;
-    for (uint32_t mm = tr.mv_mask; mm && !drop; mm &= mm - 1) {
-      const uint32_t k = (uint32_t)__builtin_ctz(mm);
-      std::set<uint32_t> vals;
-      for (uint32_t q = 0; q < nits[j]; q++) vals.insert(e.it_vid[(size_t)k * e.N + its[(size_t)j * 60 + q]]);
-      drop = vals.size() < tr.mv[k];
-    }
-    if (drop) {
-      dropped_pods.insert(dropped_pods.end(), cp[j].begin(), cp[j].end());
-      continue;
-    }
-    c->claim_nodepool[kept] = tr.np_index;
-    c->claim_pods.insert(c->claim_pods.end(), cp[j].begin(), cp[j].end());
-    c->claim_pod_offsets.push_back((uint32_t)c->claim_pods.size());
-    c->claim_its.insert(c->claim_its.end(), its.begin() + (size_t)j * 60, its.begin() + (size_t)j * 60 + nits[j]);
-    c->claim_it_offsets.push_back((uint32_t)c->claim_its.size());
-    if (e.TG && e.keys[e.k_dom].vocab.size() <= (size_t)gsd::ZVMAX && !(hdr[j].zflags & gsd::ZF_COMP)) {
-      // topology spread narrowed the zone to In[domain]: the device's zone
-      // Has already includes it (template AND pods AND topology)
-      gsh::KReq q;
-      q.comp = false;
-      q.has = gsh::Bits(e.keys[e.k_dom].vocab.words());
-      q.excl = gsh::Bits(e.keys[e.k_dom].vocab.words());
-      q.has.w[0] = hdr[j].zfull;
-      gsh::reqs_add(e, creq[j], e.k_dom, q);
-    }
-    creq[j].erase(e.k_hostname);  // FinalizeScheduling
-    c->req_text[kept] = gsh::canonical(e, creq[j]);
-    for (uint32_t r = 0; r < e.R; r++) c->claim_requests[(size_t)kept * e.R + r] = hdr[j].tot(r);
-    kept++;
-  }
-  c->claim_nodepool.resize(kept);
-  c->req_text.resize(kept);
-  c->claim_requests.resize((size_t)kept * e.R);
-  c->req_ptrs.clear();
-  for (auto& s : c->req_text) c->req_ptrs.push_back(s.c_str());
-  c->error_pods.clear();
-  for (uint32_t i = 0; i < c->ctrl.qlen; i++) c->error_pods.push_back(queue[(c->ctrl.qhead + i) % e.P]);
-  c->error_pods.insert(c->error_pods.end(), dropped_pods.begin(), dropped_pods.end());
-  std::sort(c->error_pods.begin(), c->error_pods.end());
-  for (auto& v : np_) {
-    c->node_pods.insert(c->node_pods.end(), v.begin(), v.end());
-    c->node_pod_offsets.push_back((uint32_t)c->node_pods.size());
-  }
+  std::vector<uint32_t> unplaced;
+  for (uint32_t i = 0; i < c->ctrl.qlen; i++) unplaced.push_back(queue[(c->ctrl.qhead + i) % e.P]);
+  const SolveRecords rec{log.data(),       (uint32_t)log.size(),      hdr.data(), its.data(),           nits.data(), c->ctrl.n_claims,
+                         unplaced.data(), (uint32_t)unplaced.size(), nullptr,    e.node_order.data()};
+  const gs_status ds = decode_result(c, rec, out);
+  if (ds != GS_OK) return ds;
   c->t_fetch = ms_since(t0);
-  std::memset(out, 0, sizeof(*out));
-  out->n_claims = kept;
-  out->claim_nodepool = c->claim_nodepool.data();
-  out->claim_pod_offsets = c->claim_pod_offsets.data();
-  out->claim_pods = c->claim_pods.data();
-  out->claim_it_offsets = c->claim_it_offsets.data();
-  out->claim_its = c->claim_its.data();
-  out->claim_requirements = c->req_ptrs.data();
-  out->n_resources = e.R;
-  out->resource_names = e.res_name_ids.data();
-  out->claim_requests = c->claim_requests.data();
-  out->n_nodes = e.NN;
-  out->node_pod_offsets = c->node_pod_offsets.data();
-  out->node_pods = c->node_pods.data();
-  out->n_errors = (uint32_t)c->error_pods.size();
-  out->error_pods = c->error_pods.data();
   out->checks = e.checks;
   out->pops = c->ctrl.pops;
   out->cand_evals = c->ctrl.cand_evals;

@@ -1,5 +1,6 @@
 // consolidate.cpp — consolidation entry points of libgpusched.so
-// (gs_consolidate, gs_consolidate_rerun, gs_consolidation_choose).
+// (gs_consolidate, gs_consolidate_rerun, gs_consolidation_results,
+// gs_consolidation_choose).
 //
 // <U> sigs.k8s.io/karpenter@v1.13.0 pkg/controllers/disruption:
 //   SimulateScheduling      every simulation is an independent Solve of the
@@ -365,6 +366,17 @@ void reset_sim_counts(gs_ctx* c) {
     c->cons_ready = false;
 }
 
+// a fresh overlay stamp prefix per launch; cells of 4,095 launches ago
+// could match again, so the cells are cleared when the prefix wraps
+void next_overlay_epoch(gs_ctx* c) {
+  auto& d = c->dp;
+  d.ov_epoch = (d.ov_epoch + 1u) & 0xFFFu;
+  if (!d.ov_epoch) {
+    if (c->ov_hn_bytes) HIPCHK(hipMemsetAsync(d.ov_hn, 0, c->ov_hn_bytes, c->stream));
+    d.ov_epoch = 1;
+  }
+}
+
 gs_status run_and_decide(gs_ctx* c, gs_consolidation_result* out) {
   const gsh::Encoded& e = c->enc;
   const SimPlan& sp = c->sims;
@@ -383,13 +395,7 @@ gs_status run_and_decide(gs_ctx* c, gs_consolidation_result* out) {
     HIPCHK(hipEventRecord(c->ev[1], c->stream));
     if (NS) {
       HIPCHK(hipMemsetAsync(d.sim_next, 0, sizeof(uint32_t), c->stream));
-      // a fresh overlay stamp prefix per launch; cells of 4,095 launches ago
-      // could match again, so the cells are cleared when the prefix wraps
-      d.ov_epoch = (d.ov_epoch + 1u) & 0xFFFu;
-      if (!d.ov_epoch) {
-        if (c->ov_hn_bytes) HIPCHK(hipMemsetAsync(d.ov_hn, 0, c->ov_hn_bytes, c->stream));
-        d.ov_epoch = 1;
-      }
+      next_overlay_epoch(c);
       HIPCHK(gsk_ffd(&d, sp.blocks, c->stream));
     }
     HIPCHK(hipEventRecord(c->ev[2], c->stream));
@@ -562,6 +568,104 @@ gs_status run_and_decide(gs_ctx* c, gs_consolidation_result* out) {
   return GS_OK;
 }
 
+// <U> SimulateScheduling's scheduling.Results of evaluated simulation k.  The
+// sweep keeps one SimCtrl, one header and one top 60 per simulation (with
+// sim_lds not even the add log reaches HBM), so the simulation runs again on
+// the resident upload: one wide workgroup of the simulation kernel over
+// [k, k + 1) with its queue arrays and add log in HBM, then OrderByPrice +
+// Truncate(60) of every NodeClaim it opened.  The decode is gs_fetch's; pod
+// ids are the combined list's (pending i, bound b -> n_pending + b), which the
+// kernel's records already carry.  Nothing the commands point into is touched.
+gs_status sim_results(gs_ctx* c, uint32_t sim, gs_result* out) {
+  const gsh::Encoded& e = c->enc;
+  const SimPlan& sp = c->sims;
+  const auto at = std::lower_bound(sp.evaluated.begin(), sp.evaluated.end(), sim);
+  if (at == sp.evaluated.end() || *at != sim) return fail(c, GS_E_INVALID, "simulation not evaluated on this context");
+  const uint32_t k = (uint32_t)(at - sp.evaluated.begin());
+  const uint32_t q0 = sp.pod_off[k], P = sp.pod_off[k + 1] - q0;
+  gsd::SimCtrl ct{};
+  gsd::Ctrl blk{};
+  float a = 0, b = 0;
+  try {
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipEventRecord(c->ev[0], c->stream));
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)c->dp.sim_next, (int)k, 1, c->stream));
+    next_overlay_epoch(c);
+    gsd::DevProblem d = c->dp;
+    d.n_sims = k + 1;  // the work counter starts at k: this workgroup takes k, then leaves
+    d.sim_nt = 256;    // one simulation's latency: the wide shape
+    d.sim_lds = 0;     // the add log in d.log + q0
+    d.slot_its = c->res_its;
+    d.slot_nits = c->res_nits;
+    d.slot_drop = c->res_drop;
+    HIPCHK(gsk_ffd(&d, 1, c->stream));
+    HIPCHK(hipEventRecord(c->ev[1], c->stream));
+    HIPCHK(gsk_trunc_slots(&d, trunc_lds_bytes(d.N), q0, P, c->stream));
+    HIPCHK(hipEventRecord(c->ev[2], c->stream));
+    HIPCHK(hipEventSynchronize(c->ev[2]));
+    HIPCHK(hipEventElapsedTime(&a, c->ev[0], c->ev[1]));
+    HIPCHK(hipEventElapsedTime(&b, c->ev[1], c->ev[2]));
+  } catch (const HipError& ex) {
+    reset_sim_counts(c);
+    return fail(c, GS_E_HIP, ex.msg);
+  }
+  const auto t0 = Clock::now();
+  std::vector<gsd::LogRec> log;
+  std::vector<gsd::ClaimRec> hdr;
+  std::vector<uint32_t> its, nits;
+  try {
+    HIPCHK(hipMemcpy(&ct, c->dp.sim_ctrl + k, sizeof ct, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&blk, c->dp.sim_blk, sizeof blk, hipMemcpyDeviceToHost));
+    if (ct.status != 0) reset_sim_counts(c);
+    if (ct.status == gsd::ST_POD_COUNT)
+      return fail(c, GS_E_CAPACITY, "a simulated NodeClaim would hold more than 65535 pods (16-bit pod count)");
+    if (ct.status != 0 || ct.n_log > P || ct.n_claims > P)
+      return fail(c, GS_E_HIP, "simulation kernel reported an internal error");
+    const uint32_t M = ct.n_claims;
+    log.resize(ct.n_log);
+    hdr.resize(M);
+    its.resize((size_t)M * 60);
+    nits.resize(M);
+    if (!log.empty())
+      HIPCHK(hipMemcpy(log.data(), c->dp.log + q0, log.size() * sizeof(gsd::LogRec), hipMemcpyDeviceToHost));
+    if (M) {
+      HIPCHK(hipMemcpy(hdr.data(), c->dp.c_rec + q0, M * sizeof(gsd::ClaimRec), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(its.data(), c->res_its, its.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(nits.data(), c->res_nits, M * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+  } catch (const HipError& ex) {
+    return fail(c, GS_E_HIP, ex.msg);
+  }
+  // the pods still queued at the end: the simulation's pods the log lacks
+  std::vector<uint8_t> placed(e.P, 0);
+  for (const gsd::LogRec& l : log) {
+    if (l.pod >= e.P) return fail(c, GS_E_HIP, "corrupt add log");
+    placed[l.pod] = 1;
+  }
+  std::vector<uint32_t> unplaced;
+  for (uint32_t i = 0; i < P; i++)
+    if (!placed[sp.pods[q0 + i]]) unplaced.push_back(sp.pods[q0 + i]);
+  const SolveRecords rec{log.data(),      (uint32_t)log.size(),      hdr.data(), its.data(),           nits.data(), ct.n_claims,
+                         unplaced.data(), (uint32_t)unplaced.size(), nullptr,    e.node_order.data()};
+  const gs_status ds = decode_result(c, rec, out);
+  if (ds != GS_OK) return ds;
+  // the settlement sim_fix_kernel / run_and_decide made for the command, from
+  // the decoded result: the two runs of one simulation must agree
+  uint32_t failed = 0;
+  for (uint32_t x : c->error_pods) failed += x >= c->n_pending ? 1u : 0u;
+  for (const gsd::LogRec& l : log)
+    if ((l.target & 0x80000000u) && l.pod >= c->n_pending && !e.nodes[l.target & 0x7FFFFFFFu].init) failed++;
+  if (out->n_claims != c->commands[sim].n_new_claims || failed != c->commands[sim].n_failed_pods)
+    return fail(c, GS_E_HIP, "the simulation's second run disagrees with its command");
+  out->pops = blk.pops;
+  out->t_ffd_sort_ms = out->t_ffd_scan_ms = out->t_ffd_template_ms = -1.0;  // not measured
+  out->t_ffd_ms = a;
+  out->t_truncate_ms = b;
+  out->t_fetch_ms = ms_since(t0);
+  out->t_total_ms = out->t_ffd_ms + out->t_truncate_ms + out->t_fetch_ms;
+  return GS_OK;
+}
+
 gs_status check_input(const gs_consolidation* in, std::string* err) {
   if (!in || !in->cluster) {
     *err = "null input";
@@ -613,6 +717,7 @@ gs_status gs_consolidate(gs_ctx* c, const gs_consolidation* in, gs_consolidation
   if (st != GS_OK) return fail(c, st, err);
   if (!c->shards.empty()) return sharded_consolidate(c, in, out);
   c->prepared = c->ran = false;
+  c->cons_ready = false;  // until this input is resident
   // own copies of the caller's candidate arrays (gs_consolidate_rerun)
   c->cons_cands.assign(in->candidates, in->candidates + in->n_candidates);
   c->cons_sets.assign(in->sets, in->sets + (in->mode == GS_CONSOLIDATE_EVAL ? in->n_sets : 0));
@@ -656,6 +761,16 @@ gs_status gs_consolidate_rerun(gs_ctx* c, gs_consolidation_result* out) {
   if (!c || !out || !c->cons_ready) return GS_E_INVALID;
   if (!c->shards.empty()) return sharded_consolidate(c, nullptr, out);
   return run_and_decide(c, out);
+}
+
+gs_status gs_consolidation_results(gs_ctx* c, uint32_t sim, gs_result* out) {
+  if (!c || !out) return GS_E_INVALID;
+  if (!c->cons_ready) return fail(c, GS_E_INVALID, "no consolidation is resident (gs_consolidate first)");
+  if (sim >= c->commands.size()) return fail(c, GS_E_INVALID, "simulation index out of range");
+  if (c->commands[sim].decision == GS_DECISION_SKIPPED)
+    return fail(c, GS_E_INVALID, "simulation skipped by the shard filter");
+  if (!c->shards.empty()) return sharded_results(c, sim, out);
+  return sim_results(c, sim, out);
 }
 
 gs_status gs_consolidation_choose(const gs_consolidation* in, const gs_command* commands, uint32_t n_commands,

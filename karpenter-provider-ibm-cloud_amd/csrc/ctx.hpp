@@ -33,6 +33,8 @@ extern "C" hipError_t gsk_init_ffdw(uint32_t lds_total);
 extern "C" uint32_t gsk_ffdw_dyn_lds_max(void);
 extern "C" hipError_t gsk_ffdw(const gsd::DevProblem* d, uint32_t ch, hipStream_t s);
 extern "C" hipError_t gsk_trunc(const gsd::DevProblem* d, uint32_t lds_bytes, uint32_t n_slots, hipStream_t s);
+extern "C" hipError_t gsk_trunc_slots(const gsd::DevProblem* d, uint32_t lds_bytes, uint32_t slot0, uint32_t n_slots,
+                                      hipStream_t s);
 extern "C" hipError_t gsk_mv_rows(const gsd::DevProblem* d, hipStream_t s);
 extern "C" hipError_t gsk_queue_records(const gsd::DevProblem* d, hipStream_t s);
 extern "C" hipError_t gsk_merge_shards(const gsd::ShardMerge* m, hipStream_t s);
@@ -144,6 +146,11 @@ struct gs_ctx {
   uint32_t* h_its = nullptr;
   uint32_t* h_nits = nullptr;
   double t_sim = 0;
+  // gs_consolidation_results: the re-run simulation's per-NodeClaim top 60
+  // (device; one slot per pod of the largest simulation)
+  uint32_t* res_its = nullptr;
+  uint32_t* res_nits = nullptr;
+  uint32_t* res_drop = nullptr;
 
   // gs_create_filter: grow-once device arena and result storage
   void* cf_dev = nullptr;
@@ -234,6 +241,26 @@ CandTable build_cand_table(const gs_problem* p, const uint32_t* cands, uint32_t 
 int32_t choose_commands(const CandTable& t, const gs_consolidation* in, const gs_command* commands,
                         const uint32_t* options, const double* prices, std::vector<uint32_t>* multi);
 gsh::Err capacity_check(const gsh::Encoded& e);
+// One Solve's device records, copied to the host: the add log, the NodeClaim
+// headers with their OrderByPrice top 60 ([n_claims][60] / [n_claims]), the
+// pods still queued at the end, and the maps from the records' pod ids
+// (nullptr: they are the caller's already) and node positions to the caller's
+// indices.
+struct SolveRecords {
+  const gsd::LogRec* log;
+  uint32_t n_log;
+  const gsd::ClaimRec* hdr;
+  const uint32_t* its;
+  const uint32_t* nits;
+  uint32_t n_claims;
+  const uint32_t* unplaced;
+  uint32_t n_unplaced;
+  const uint32_t* pod_index;
+  const uint32_t* node_index;
+};
+gs_status decode_result(gs_ctx* c, const SolveRecords& r, gs_result* out);
+// multi.cpp: gs_consolidation_results on the shard that evaluated `sim`
+gs_status sharded_results(gs_ctx* c, uint32_t sim, gs_result* out);
 uint32_t trunc_lds_bytes(uint32_t N);
 // encode output -> device arena; `sims` non-null: consolidation arenas
 void upload_problem(gs_ctx* c, const SimPlan* sims);

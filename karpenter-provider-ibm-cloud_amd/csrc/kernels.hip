@@ -265,11 +265,13 @@ __global__ __launch_bounds__(BLOCK) void feas_kernel(DevProblem d, uint32_t stat
 // prices); output slot s.  With minValues (all_slots): block j truncates
 // NodeClaim arena slot j of whichever simulation holds it and flags a top 60
 // that misses a minimum (<U> Results.TruncateInstanceTypes drops it); the
-// sim_fix kernel then settles each simulation.
-extern "C" __global__ __launch_bounds__(BLOCK) void trunc_kernel(DevProblem d, uint32_t all_slots) {
+// sim_fix kernel then settles each simulation.  Block b takes arena slot
+// slot0 + b and writes output slot b: slot0 is 0 but for
+// gs_consolidation_results, which truncates one simulation's NodeClaims.
+extern "C" __global__ __launch_bounds__(BLOCK) void trunc_kernel(DevProblem d, uint32_t all_slots, uint32_t slot0) {
   extern __shared__ uint64_t keys[];
   __shared__ uint32_t cnt;
-  uint32_t j = blockIdx.x;  // claim
+  uint32_t j = blockIdx.x + slot0;  // claim
   const uint32_t o = blockIdx.x;  // output slot
   if (all_slots) {
     // the simulation whose arena holds slot j: last s with sim_pod_off[s] <= j
@@ -330,9 +332,9 @@ extern "C" __global__ __launch_bounds__(BLOCK) void trunc_kernel(DevProblem d, u
   }
   const uint32_t take = n < 60 ? n : 60;
   if (all_slots) {
-    for (uint32_t i = tid; i < take; i += BLOCK) d.slot_its[(size_t)j * 60 + i] = d.rank_to_it[(uint32_t)keys[i]];
+    for (uint32_t i = tid; i < take; i += BLOCK) d.slot_its[(size_t)o * 60 + i] = d.rank_to_it[(uint32_t)keys[i]];
     if (tid == 0) {
-      d.slot_nits[j] = take;
+      d.slot_nits[o] = take;
       // SatisfiesMinValues on the top 60: distinct values per minimum key
       const TmplRec& tr = d.tmpl[h.tmpl];
       bool ok = true;
@@ -353,7 +355,7 @@ extern "C" __global__ __launch_bounds__(BLOCK) void trunc_kernel(DevProblem d, u
         }
         ok = nd >= tr.mv[k];
       }
-      d.slot_drop[j] = ok ? 0u : 1u;
+      d.slot_drop[o] = ok ? 0u : 1u;
     }
     return;
   }
@@ -537,12 +539,22 @@ extern "C" hipError_t gsk_merge_shards(const ShardMerge* m, hipStream_t s) {
 extern "C" hipError_t gsk_trunc(const DevProblem* d, uint32_t lds_bytes, uint32_t n_slots, hipStream_t s) {
   if (d->n_sims && d->any_mv) {
     if (!n_slots) return hipSuccess;
-    hipLaunchKernelGGL(trunc_kernel, dim3(n_slots), dim3(BLOCK), lds_bytes, s, *d, 1u);
+    hipLaunchKernelGGL(trunc_kernel, dim3(n_slots), dim3(BLOCK), lds_bytes, s, *d, 1u, 0u);
     hipLaunchKernelGGL(sim_fix_kernel, dim3((d->n_sims + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, *d);
     return hipGetLastError();
   }
   const uint32_t grid = d->n_sims ? d->n_sims : d->claim_cap;
   if (!grid) return hipSuccess;
-  hipLaunchKernelGGL(trunc_kernel, dim3(grid), dim3(BLOCK), lds_bytes, s, *d, 0u);
+  hipLaunchKernelGGL(trunc_kernel, dim3(grid), dim3(BLOCK), lds_bytes, s, *d, 0u, 0u);
+  return hipGetLastError();
+}
+
+// every NodeClaim of one simulation (arena slots slot0 .. slot0 + n_slots) into
+// slots 0.. of d->slot_its / slot_nits / slot_drop (gs_consolidation_results;
+// d->n_sims - 1 is that simulation)
+extern "C" hipError_t gsk_trunc_slots(const DevProblem* d, uint32_t lds_bytes, uint32_t slot0, uint32_t n_slots,
+                                      hipStream_t s) {
+  if (!n_slots) return hipSuccess;
+  hipLaunchKernelGGL(trunc_kernel, dim3(n_slots), dim3(BLOCK), lds_bytes, s, *d, 1u, slot0);
   return hipGetLastError();
 }

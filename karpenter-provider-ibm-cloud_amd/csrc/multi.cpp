@@ -203,4 +203,15 @@ gs_status sharded_consolidate(gs_ctx* c, const gs_consolidation* in, gs_consolid
   return GS_OK;
 }
 
+// the shard that evaluated the simulation re-runs it; the result lives in
+// that shard's storage
+gs_status sharded_results(gs_ctx* c, uint32_t sim, gs_result* out) {
+  const size_t k = sim % c->shards.size();
+  const gs_status st = gs_consolidation_results(c->shards[k], sim, out);
+  if (st == GS_OK) return st;
+  char buf[512];
+  gs_last_error(c->shards[k], buf, sizeof buf);
+  return fail(c, st, "shard " + std::to_string(k) + ": " + buf);
+}
+
 }  // namespace gsc

@@ -49,6 +49,46 @@ def n_multi_sims(n_candidates, max_candidates=100):
     return mx
 
 
+def sub_problem(problem, cands):
+    """The Solve one simulation runs (<U> SimulateScheduling): the cluster's
+    pending pods plus the candidates' bound pods (candidates in set order, a
+    candidate's pods in ascending index) over the nodes that are not
+    candidates, the other bound pods kept on their nodes.  A view like
+    Problem.with_pods: the pools stay shared.
+    -> (Problem, pod_index_map, node_index_map): pod i of the view is pod
+    pod_index_map[i] in gs_consolidation_results' numbering (pending i, bound b
+    -> n_pods + b), node j of the view is cluster node node_index_map[j]"""
+    import copy
+    cands = np.asarray(cands, dtype=np.int64).reshape(-1)
+    n_nodes, n_pending = len(problem.nodes), len(problem.pods)
+    bn = problem.bound_node.astype(np.int64)
+    removed = np.zeros(n_nodes, dtype=bool)
+    removed[cands] = True
+    # the bound pods of each candidate, candidates in the order given
+    by_node = np.argsort(bn, kind="stable")
+    lo = np.searchsorted(bn[by_node], cands, side="left")
+    cnt = np.searchsorted(bn[by_node], cands, side="right") - lo
+    moved = by_node[np.repeat(lo, cnt) + np.arange(cnt.sum()) - np.repeat(np.cumsum(cnt) - cnt, cnt)]
+    stay = np.flatnonzero(~removed[bn])
+    node_map = np.flatnonzero(~removed)
+    new_index = np.cumsum(~removed) - 1
+    q = copy.copy(problem)
+    q.pods = np.concatenate([problem.pods, problem.bound_pods[moved]])
+    q.nodes = problem.nodes[node_map].copy()
+    q.bound_pods = problem.bound_pods[stay].copy()
+    q.bound_node = new_index[bn[stay]].astype(np.uint32)
+    q.struct = abi.GsProblem()
+    C.memmove(C.byref(q.struct), C.byref(problem.struct), C.sizeof(abi.GsProblem))
+    st = q.struct
+    for name in ("pods", "nodes", "bound_pods"):
+        arr = getattr(q, name)
+        setattr(st, name, arr.ctypes.data if len(arr) else None)
+        setattr(st, "n_" + name, len(arr))
+    st.bound_pod_node = q.bound_node.ctypes.data if len(q.bound_node) else None
+    pod_map = np.concatenate([np.arange(n_pending, dtype=np.int64), n_pending + moved])
+    return q, pod_map, node_map
+
+
 def pack_commands(cmds):
     """fixed-size records (for an all-gather across ranks): [n, 9 + 2*60] float64"""
     rec = np.zeros((len(cmds), 9 + 120), dtype=np.float64)

@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(HERE, os.environ.get("GPUSCHED_LIB", "libgpusched.so"))
 
 EXPORTS = ["gs_create", "gs_destroy", "gs_prepare", "gs_run", "gs_fetch", "gs_solve", "gs_feasibility",
            "gs_last_error", "gs_version", "gs_validate", "gs_abi_sizes", "gs_last_run_ms",
-           "gs_consolidate", "gs_consolidate_rerun", "gs_consolidation_choose", "gs_feasibility_shard",
+           "gs_consolidate", "gs_consolidate_rerun", "gs_consolidation_results", "gs_consolidation_choose", "gs_feasibility_shard",
            "gs_feasibility_shard_device", "gs_rank_instance_types", "gs_create_filter", "gs_build_catalog", "gs_build_id"]
 
 
@@ -102,6 +102,8 @@ def load():
         L.gs_consolidate.restype = C.c_int
         L.gs_consolidate_rerun.argtypes = [vp, C.POINTER(abi.GsConsolidationResult)]
         L.gs_consolidate_rerun.restype = C.c_int
+        L.gs_consolidation_results.argtypes = [vp, C.c_uint32, C.POINTER(abi.GsResult)]
+        L.gs_consolidation_results.restype = C.c_int
         L.gs_consolidation_choose.argtypes = [C.POINTER(abi.GsConsolidation), C.POINTER(abi.GsCommand), C.c_uint32,
                                               C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -176,6 +178,7 @@ class Solver:
         if st != abi.GS_OK:
             raise GpuSchedError(st, "gs_create failed (no gfx950 device?)")
         self.problem = None
+        self.cluster = None  # the cluster of the last consolidate (resource names of its results)
 
     def close(self):
         if self.ctx:
@@ -231,6 +234,7 @@ class Solver:
     def consolidate(self, cin):
         """gs_consolidate: (commands, chosen, multi_options, raw result)"""
         res = abi.GsConsolidationResult()
+        self.cluster = cin.problem
         self._check(self.L.gs_consolidate(self.ctx, C.byref(cin.struct), C.byref(res)))
         return abi.commands_to_list(res), int(res.chosen), _multi(res), res
 
@@ -242,6 +246,15 @@ class Solver:
         if raw:
             return res
         return abi.commands_to_list(res), int(res.chosen), _multi(res), res
+
+    def consolidation_results(self, sim):
+        """gs_consolidation_results: the scheduling Results of simulation `sim`
+        of the last consolidate / consolidate_rerun -> (dict, raw gs_result).
+        Pods are numbered pending i, bound b -> n_pods + b; nodes are the
+        cluster's (consolidation.sub_problem's maps lead there)"""
+        res = abi.GsResult()
+        self._check(self.L.gs_consolidation_results(self.ctx, int(sim), C.byref(res)))
+        return abi.result_to_dict(res, self.cluster), res
 
     def create_filter(self, problem, raw=False):
         """gs_create_filter over problem.claim_queries: per claim
