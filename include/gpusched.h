@@ -524,6 +524,48 @@ gs_status gs_fetch(gs_ctx* ctx, gs_result* out);
 /* prepare + run + fetch */
 gs_status gs_solve(gs_ctx* ctx, const gs_problem* problem, gs_result* out);
 
+/* ---- a batch of independent Solves: several clusters, one device ----------
+ * The reference interface is scheduling.NewScheduler(...).Solve(pods), once
+ * per cluster: every problem of a batch has its own catalog, NodePools, nodes
+ * and pods, and its result is the one gs_solve gives for it alone.  The
+ * problems run side by side, one workgroup each, in a number of kernel
+ * launches that does not depend on how many they are.  The batch is separate
+ * from the context's single prepared problem: neither disturbs the other. */
+#define GS_BATCH_MAX 4096u
+typedef struct gs_batch_stats {
+  uint32_t n_problems;   /* of the last batch prepare */
+  uint32_t n_accepted;   /* slots whose status is GS_OK */
+  uint32_t n_batched;    /* accepted slots the batched kernels solved in the last run */
+  uint32_t n_fallback;   /* accepted slots solved one at a time (the single-problem run path):
+                            more than 6,144 existing nodes, a context with GS_CFG_BLOCK_SOLVE or
+                            GS_CFG_CLAIMS_HBM, or more NodeClaims than the slot's LDS holds */
+  uint32_t n_groups;     /* distinct kernel instantiations among the batched slots */
+  uint32_t n_launches;   /* kernel launches of the batched part of the last run */
+  double prepare_ms;     /* wall clock of the last batch prepare */
+  double run_ms;         /* wall clock of the last batch run */
+  double device_ms;      /* first to last batched kernel of the last run (HIP events) */
+} gs_batch_stats;
+/* Scheduler.Solve inputs of n independent clusters: encode + upload each;
+ * status[i] receives problem i's own gs_status.  A refused or invalid problem
+ * (GS_E_UNSUPPORTED, GS_E_INVALID, GS_E_CAPACITY) fails neither the call nor
+ * the other slots.  Returns GS_OK unless the call itself is invalid (NULL
+ * arguments, GS_E_CAPACITY for n over GS_BATCH_MAX, a context with shards) or
+ * HIP fails.  n = 0 is valid.  A second call replaces the first batch; the
+ * caller's arrays are not kept. */
+gs_status gs_batch_prepare(gs_ctx* ctx, const gs_problem* const* problems, uint32_t n, gs_status* status);
+/* Scheduler.Solve of every accepted slot; can be called repeatedly */
+gs_status gs_batch_run(gs_ctx* ctx);
+/* slot i's scheduling.Results, as the single-problem fetch returns them, or
+ * slot i's status when it was refused; valid until the next batch prepare, the
+ * next fetch of the same slot, or gs_destroy */
+gs_status gs_batch_fetch(gs_ctx* ctx, uint32_t i, gs_result* out);
+/* slot i's message (why its problem was refused, or why its fetch failed) */
+size_t gs_batch_error(const gs_ctx* ctx, uint32_t i, char* buf, size_t len);
+/* counters and times of the last batch prepare / run */
+gs_status gs_batch_last_run(const gs_ctx* ctx, gs_batch_stats* out);
+/* sizeof the stats struct, for a binding's layout check */
+uint32_t gs_batch_stats_size(void);
+
 /* static feasibility matrix only (K1/K2) on a prepared problem */
 gs_status gs_feasibility(gs_ctx* ctx, gs_feas_result* out);
 /* one instance-type column shard of it: only words

@@ -11,7 +11,7 @@ gs_status fail(gs_ctx* c, gs_status s, const std::string& m) {
   return s;
 }
 
-void upload_problem(gs_ctx* c, const SimPlan* sims) {
+void upload_problem(gs_ctx* c, const SimPlan* sims, bool records) {
   auto& e = c->enc;
   auto& d = c->dp;
   c->plan.clear();
@@ -251,7 +251,7 @@ void upload_problem(gs_ctx* c, const SimPlan* sims) {
     c->alloc(c->res_drop, d.max_claims);
   }
   c->commit();
-  if (!sims) {
+  if (!sims && records) {
     HIPCHK(gsk_queue_records(&d, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
@@ -590,6 +590,8 @@ gs_status gs_create(const gs_config* cfg, gs_ctx** out) {
     HIPCHK(gsk_init_ffd(kLdsBytes));
     HIPCHK(gsk_init_ffdw(kLdsBytes));
     HIPCHK(gsk_init_trunc(65536));
+    HIPCHK(gsk_init_batch(65536));
+    HIPCHK(gsk_init_ffdw_batch(kLdsBytes));
   } catch (const HipError& e) {
     delete c;
     return GS_E_HIP;
@@ -645,6 +647,7 @@ void gs_destroy(gs_ctx* c) {
   for (gs_ctx* s : c->shards) gs_destroy(s);
   c->shards.clear();
   (void)hipSetDevice(c->device);
+  batch_destroy(c);
   c->free_all();
   if (c->arena) (void)hipFree(c->arena);
   if (c->stage) (void)hipHostFree(c->stage);

@@ -38,6 +38,19 @@ extern "C" hipError_t gsk_trunc_slots(const gsd::DevProblem* d, uint32_t lds_byt
 extern "C" hipError_t gsk_mv_rows(const gsd::DevProblem* d, hipStream_t s);
 extern "C" hipError_t gsk_queue_records(const gsd::DevProblem* d, hipStream_t s);
 extern "C" hipError_t gsk_merge_shards(const gsd::ShardMerge* m, hipStream_t s);
+// batch_kernels.hip: the grid kernels over a device array of problems
+extern "C" hipError_t gsk_init_batch(uint32_t trunc_lds_bytes);
+extern "C" uint32_t gsk_feas_lp(uint32_t W);
+extern "C" hipError_t gsk_feas_batch(const gsd::DevProblem* ds, uint32_t n, uint32_t lp, uint64_t max_cursors,
+                                     uint64_t max_pairs, hipStream_t s);
+extern "C" hipError_t gsk_init_state_batch(const gsd::DevProblem* ds, uint32_t n, hipStream_t s);
+extern "C" hipError_t gsk_queue_records_batch(const gsd::DevProblem* ds, uint32_t n, uint32_t max_pods, hipStream_t s);
+extern "C" hipError_t gsk_init_ffdw_batch(uint32_t lds_total);
+extern "C" uint32_t gsk_ffdw_batch_dyn_lds_max(void);
+extern "C" hipError_t gsk_ffdw_batch(const gsd::DevProblem* ds, uint32_t n, uint32_t R, uint32_t topo, uint32_t wide,
+                                     uint32_t lds, hipStream_t s);
+extern "C" hipError_t gsk_trunc_batch(const gsd::DevProblem* ds, uint32_t n, uint32_t max_slots, uint32_t lds_bytes,
+                                      hipStream_t s);
 
 namespace gsc {
 
@@ -94,12 +107,16 @@ struct SimPlan {
   uint32_t multi_max = 0;                   // MULTI: firstNConsolidationOption's max
 };
 
+struct Batch;  // batch.cpp: the slots of gs_batch_*
+void batch_destroy(gs_ctx* c);
+
 }  // namespace gsc
 
 struct gs_ctx {
   int device = 0;
   uint32_t cfg_flags = 0;  // gs_config.flags
   std::vector<gs_ctx*> shards;  // gs_config.n_shards > 1: one child context per shard (multi.cpp)
+  gsc::Batch* batch = nullptr;  // gs_batch_*: one child context per slot, on this context's stream and events (batch.cpp)
   std::vector<ncclComm_t> comms;  // GS_CFG_RCCL: one communicator rank per shard (ncclCommInitAll)
   std::string err;
   hipStream_t stream = nullptr;
@@ -263,7 +280,9 @@ gs_status decode_result(gs_ctx* c, const SolveRecords& r, gs_result* out);
 gs_status sharded_results(gs_ctx* c, uint32_t sim, gs_result* out);
 uint32_t trunc_lds_bytes(uint32_t N);
 // encode output -> device arena; `sims` non-null: consolidation arenas
-void upload_problem(gs_ctx* c, const SimPlan* sims);
+// (records: gather the Solve's first-pass queue records after the upload;
+// false for a batch slot, whose batch gathers every slot's in one launch)
+void upload_problem(gs_ctx* c, const SimPlan* sims, bool records = true);
 
 }  // namespace gsc
 

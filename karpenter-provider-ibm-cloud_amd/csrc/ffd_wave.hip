@@ -5,25 +5,8 @@
 
 using namespace gsd;
 
-// Grid-wide reset of the Solve's working state (queue, per-pod counters,
-// NodePool remaining limits, existing-node copies, hostname counts): the
-// single-wave kernel starts from it.
-extern "C" __global__ __launch_bounds__(256) void ffd_init_kernel(DevProblem d) {
-  const uint32_t stride = gridDim.x * blockDim.x;
-  const uint32_t i0 = blockIdx.x * blockDim.x + threadIdx.x;
-  for (uint32_t i = i0; i < d.P; i += stride) {
-    d.queue[i] = d.queue0[i];
-    d.last_epoch[i] = 0;
-    d.last_len[i] = 0;
-    d.cur_var[i] = d.var_begin[i];
-  }
-  for (uint32_t i = i0; i < d.T * d.R; i += stride) d.t_rem[i] = d.tmpl[i / d.R].limits[i % d.R];
-  for (uint32_t i = i0; i < d.NN; i += stride) d.nodes[i] = d.nodes0[i];
-  for (uint32_t i = i0; i < d.NN * d.F; i += stride) d.n_fk[i] = d.n_fk0[i];
-  for (uint32_t i = i0; i < d.TGH * d.NN; i += stride) d.hn[i] = d.hn0[i];
-  if (d.any_vol)
-    for (uint32_t i = i0; i < d.NN; i += stride) d.n_vol[i] = d.n_vol0[i];
-}
+// the Solve's state reset (shared with the batched kernels of batch_kernels.hip)
+#include "init_kernel.hpp"
 
 
 // ---------------------------------------------------------------- launchers
@@ -54,6 +37,9 @@ extern "C" hipError_t gsk_init_ffdw(uint32_t lds_total) {
 }
 
 extern "C" uint32_t gsk_ffdw_dyn_lds_max(void) { return g_ffdw_dyn_max; }
+
+// whether option rows of W words take the wide instantiation (a batch groups its problems by it)
+extern "C" uint32_t gsk_ffdw_wide(uint32_t W) { return W > WREG ? 1u : 0u; }
 
 // the single-wave provisioning Solve: grid-wide state reset, then one wave;
 // ch: the claim scan state in HBM (d->ch_* allocated, claim_cap slots)

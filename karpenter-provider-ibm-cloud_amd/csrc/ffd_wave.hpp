@@ -105,11 +105,24 @@ __device__ __forceinline__ void vst(uint32_t* p, uint32_t x) { *(volatile lds_u3
 // loads from the constant cache) and the pod's variant fields from the
 // record lane (readlane) where they use them, instead of holding ~100
 // scalar values across the loop (which spills them into VGPR lanes).
+#ifdef GS_WAVE_BATCH
+// the batched form (ffd_wave_batch_r.hip): the only kernel argument is the
+// device array of problems, the workgroup's own is element blockIdx.x.  The
+// array is not written while the kernel runs, so it is read through the
+// constant address space as the kernel arguments are.
+__device__ __forceinline__ KArg karg() {
+  const uint64_t ds = *(const __attribute__((address_space(4))) uint64_t*)__builtin_amdgcn_kernarg_segment_ptr();
+  KArg p = (KArg)(ds + (uint64_t)__builtin_amdgcn_readfirstlane(blockIdx.x) * sizeof(DevProblem));
+  asm volatile("" : "+s"(p));
+  return p;
+}
+#else
 __device__ __forceinline__ KArg karg() {
   KArg p = (KArg)__builtin_amdgcn_kernarg_segment_ptr();
   asm volatile("" : "+s"(p));
   return p;
 }
+#endif
 // an opaque copy: readlanes of it are not merged with earlier ones
 __device__ __forceinline__ uint32_t fresh(uint32_t x) {
   asm volatile("" : "+v"(x));
@@ -862,8 +875,22 @@ __device__ __forceinline__ bool pivot_touched(uint32_t modkind, uint32_t modpos,
 // WIDE: option rows of more than WREG words (the launcher picks it from d.W):
 // the narrow instantiation keeps a candidate's words in registers and
 // carries none of the wide rows' lane-split code, and the other way round
+// GS_WAVE_BATCH selects the batched signature: one workgroup per problem of
+// the device array ds, the body unchanged (it keeps all state in its own LDS
+// and in its problem's own HBM arrays)
 template <uint32_t RR, bool TOPO, bool CH = false, bool WIDE = false>
+#ifdef GS_WAVE_BATCH
+__global__ __launch_bounds__(128, 1) void ffdw_batch_kernel(const DevProblem* __restrict__ ds) {
+  DevProblem d;  // scalar loads through the constant address space, as kernel arguments arrive
+  {
+    static_assert(sizeof(DevProblem) % 8 == 0, "DevProblem copied as 8-byte words");
+    const __attribute__((address_space(4))) uint64_t* src = (const __attribute__((address_space(4))) uint64_t*)karg();
+#pragma unroll
+    for (uint32_t i = 0; i < sizeof(DevProblem) / 8; i++) ((uint64_t*)&d)[i] = src[i];
+  }
+#else
 __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
+#endif
   extern __shared__ uint64_t lds64[];
   __shared__ Frame s_stk[64];
 #ifdef GS_SORT_TL

@@ -17,7 +17,9 @@ LIB_PATH = os.path.join(HERE, os.environ.get("GPUSCHED_LIB", "libgpusched.so"))
 EXPORTS = ["gs_create", "gs_destroy", "gs_prepare", "gs_run", "gs_fetch", "gs_solve", "gs_feasibility",
            "gs_last_error", "gs_version", "gs_validate", "gs_abi_sizes", "gs_last_run_ms",
            "gs_consolidate", "gs_consolidate_rerun", "gs_consolidation_results", "gs_consolidation_choose", "gs_feasibility_shard",
-           "gs_feasibility_shard_device", "gs_rank_instance_types", "gs_create_filter", "gs_build_catalog", "gs_build_id"]
+           "gs_feasibility_shard_device", "gs_rank_instance_types", "gs_create_filter", "gs_build_catalog", "gs_build_id",
+           "gs_batch_prepare", "gs_batch_run", "gs_batch_fetch", "gs_batch_error", "gs_batch_last_run",
+           "gs_batch_stats_size"]
 
 
 def source_digest():
@@ -108,6 +110,18 @@ def load():
                                               C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.gs_consolidation_choose.restype = C.c_int
+        L.gs_batch_prepare.argtypes = [vp, C.POINTER(C.POINTER(abi.GsProblem)), C.c_uint32, C.POINTER(C.c_int)]
+        L.gs_batch_prepare.restype = C.c_int
+        L.gs_batch_run.argtypes = [vp]
+        L.gs_batch_run.restype = C.c_int
+        L.gs_batch_fetch.argtypes = [vp, C.c_uint32, C.POINTER(abi.GsResult)]
+        L.gs_batch_fetch.restype = C.c_int
+        L.gs_batch_error.argtypes = [vp, C.c_uint32, C.c_char_p, C.c_size_t]
+        L.gs_batch_error.restype = C.c_size_t
+        L.gs_batch_last_run.argtypes = [vp, C.POINTER(abi.GsBatchStats)]
+        L.gs_batch_last_run.restype = C.c_int
+        L.gs_batch_stats_size.argtypes = []
+        L.gs_batch_stats_size.restype = C.c_uint32
         _lib = L
     return _lib
 
@@ -179,6 +193,7 @@ class Solver:
             raise GpuSchedError(st, "gs_create failed (no gfx950 device?)")
         self.problem = None
         self.cluster = None  # the cluster of the last consolidate (resource names of its results)
+        self.batch_problems = []  # the problems of the last batch_prepare
 
     def close(self):
         if self.ctx:
@@ -230,6 +245,42 @@ class Solver:
         self.prepare(problem)
         self.run()
         return self.fetch()
+
+    # ---- a batch of independent Solves (several clusters, one device)
+    def batch_prepare(self, problems):
+        """gs_batch_prepare: encode + upload every problem -> the list of
+        per-slot statuses (a refused slot fails neither the call nor the others)"""
+        n = len(problems)
+        self.batch_problems = list(problems)
+        ptrs = (C.POINTER(abi.GsProblem) * max(n, 1))(*[C.pointer(p.struct) for p in problems])
+        status = (C.c_int * max(n, 1))()
+        self._check(self.L.gs_batch_prepare(self.ctx, ptrs, n, status))
+        return [int(status[i]) for i in range(n)]
+
+    def batch_run(self):
+        """gs_batch_run: every accepted slot"""
+        self._check(self.L.gs_batch_run(self.ctx))
+
+    def batch_error(self, i):
+        """gs_batch_error: slot i's message"""
+        buf = C.create_string_buffer(1024)
+        self.L.gs_batch_error(self.ctx, int(i), buf, 1024)
+        return buf.value.decode()
+
+    def batch_fetch(self, i):
+        """gs_batch_fetch: slot i's result -> (dict, raw gs_result); raises
+        with the slot's own status and message when it was refused"""
+        res = abi.GsResult()
+        st = self.L.gs_batch_fetch(self.ctx, int(i), C.byref(res))
+        if st != abi.GS_OK:
+            raise GpuSchedError(st, self.batch_error(i))
+        return abi.result_to_dict(res, self.batch_problems[i]), res
+
+    def batch_stats(self):
+        """gs_batch_last_run -> dict of the gs_batch_stats fields"""
+        out = abi.GsBatchStats()
+        self._check(self.L.gs_batch_last_run(self.ctx, C.byref(out)))
+        return {name: getattr(out, name) for name, _ in abi.GsBatchStats._fields_}
 
     def consolidate(self, cin):
         """gs_consolidate: (commands, chosen, multi_options, raw result)"""
