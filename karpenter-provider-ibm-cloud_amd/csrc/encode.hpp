@@ -10,6 +10,7 @@
 
 #include "../../include/gpusched.h"
 #include "layout.hpp"
+#include "par.hpp"
 
 namespace gsh {
 
@@ -183,17 +184,24 @@ bool label_is_wellknown(const std::string& k);
 std::string label_normalize(const std::string& k);
 bool go_atoi64(const std::string& s, int64_t* out);
 
-// algebra (exposed for decode)
+// the requirement algebra (reqs.cpp; the encoder's units, decode, filter.hip)
+// values of a vocabulary within (gt, lt)
+Bits within_mask(const Vocab& v, bool hg, int64_t gt, bool hl, int64_t lt);
+KReq make_kreq(const Vocab& v, int op, const std::vector<uint32_t>& vals, int64_t bound);
 KReq kreq_intersect(const Vocab& v, const KReq& a, const KReq& b);
 void reqs_add(const Encoded& e, Reqs& r, uint32_t key, const KReq& q);
+void reqs_add_all(const Encoded& e, Reqs& r, const Reqs& o);
+// <U> Requirements.Compatible(incoming, AllowUndefinedWellKnownLabels if allow_wk)
+bool reqs_compatible(const Encoded& e, const Reqs& r, const Reqs& in, bool allow_wk);
 std::string canonical(const Encoded& e, const Reqs& r);
-
-// host -> host copies of an upload image (gs_ctx::commit), split over the
-// encoder's threads when large
-struct HostCopy {
-  const void* src;
-  size_t off, bytes;
-};
-void host_copy_parallel(void* dst_base, const HostCopy* copies, size_t n);
+inline bool len_zero(const KReq& q) { return !q.comp && q.has.none(); }
+inline int op_of(const KReq& q) {
+  if (q.comp) return q.excl.none() ? GS_OP_EXISTS : GS_OP_NOTIN;
+  return q.has.none() ? GS_OP_DOES_NOT_EXIST : GS_OP_IN;
+}
+inline bool exempt(const KReq& q) {
+  int o = op_of(q);
+  return o == GS_OP_NOTIN || o == GS_OP_DOES_NOT_EXIST;
+}
 
 }  // namespace gsh

@@ -16,7 +16,7 @@ NodeClaim its domain).
 
 The oracle restates this (oracle/solve.cpp topo_update); the product encodes
 such groups as lazy groups that the kernels activate at the Relax
-(encode.cpp pod_phase_b2, ffd_common.hpp topo_relaxed / topo_mark_unknown).
+(encode_pods.cpp pod_phase_b2, ffd_common.hpp topo_relaxed / topo_mark_unknown).
 Parity against upstream itself stays unpinned (no Go toolchain here).
 """
 import pytest

@@ -1,10 +1,15 @@
-// encode_harness.cpp — host-only driver of the Solve encoder (encode.cpp)
+// encode_harness.cpp — host-only driver of the Solve encoder (encode.cpp and
+// the units it drives: vocab, catalog, taints, pods, nodes, topology, reqs, par)
 // over gs_problem dumps written by gpusched.problem.Problem.dump().
-// Built with g++ (no HIP) for two uses:
+// Built with g++ (no HIP) for three uses:
 //  * sanitizers: tests/test_encode_sanitizers.py builds it with
 //    -fsanitize=address,undefined and runs every dump once;
-//  * profiling: build with -O2 -pg and run a dump many times (gprof).
-// Usage: encode_harness [-n reps] dump...   prints "<status> <ms> <path>" per dump.
+//  * profiling: build with -O2 -pg and run a dump many times (gprof);
+//  * comparing encodings (two builds, two thread counts): -d prints a digest
+//    of everything the encoder produced.
+// Usage: encode_harness [-n reps] [-d] dump...   prints "<status> <ms> <path>"
+// per dump; with -d then the message, one "<array> <length> <FNV-1a 64>" line
+// per Encoded array and one "host" line over the host-only decode state.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -81,13 +86,77 @@ bool load(const char* path, Dump& d) {
   return true;
 }
 
+// 64-bit FNV-1a
+struct Fnv {
+  uint64_t h = 0xcbf29ce484222325ull;
+  void bytes(const void* p, size_t n) {
+    for (size_t i = 0; i < n; i++) h = (h ^ ((const unsigned char*)p)[i]) * 0x100000001b3ull;
+  }
+  void str(const std::string& s) {
+    u64(s.size());
+    bytes(s.data(), s.size());
+  }
+  void u64(uint64_t x) { bytes(&x, 8); }
+};
+
+template <class T>
+void digest_array(const char* name, const std::vector<T>& v) {
+  Fnv f;
+  f.bytes(v.data(), v.size() * sizeof(T));
+  printf("  %s %zu %016llx\n", name, v.size(), (unsigned long long)f.h);
+}
+
+void digest(const gsh::Err& er, const gsh::Encoded& e) {
+  printf("  msg %s\n", er.msg.c_str());
+#define A(m) digest_array(#m, e.m)
+  A(it_keys), A(free_keys), A(cat_zone), A(cat_ct), A(res_name_ids);
+  A(it_vid), A(it_prank), A(it_namerank), A(rank_to_it), A(thr_off), A(it_dvid), A(it_ndv);
+  A(n_vol), A(pod_vol), A(pod_vfresh);
+  A(it_alloc), A(it_cap), A(thr_val), A(fk_ival), A(it_pair), A(slot_set), A(thr_set), A(fk_isint);
+  A(prices), A(t_limopts), A(tmpl), A(t_opts), A(t_fk), A(pod_req), A(var_begin), A(var_count), A(queue0);
+  A(var_sv), A(vars), A(itmask), A(var_itclass), A(itclass_mask), A(fk_entries);
+  A(node_order), A(nodes), A(n_fk);
+  A(tgroups), A(tg_list), A(zcnt0), A(htot0), A(lazy_slot), A(var_lz_off), A(lz_idx), A(lz_mind);
+  A(zone_order), A(zone_cat), A(hn0), A(zn_cnt), A(zone_nodes);
+#undef A
+  // host-only state: vocabulary, sizes and flags, then the requirement sets decode reads
+  Fnv f;
+  for (auto& k : e.keys) {
+    f.str(k.name);
+    for (auto& v : k.vocab.vals) f.str(v);
+    f.u64(((uint64_t)k.cls << 40) | ((uint64_t)k.wellknown << 32) | (uint32_t)k.slot);
+    f.u64((uint32_t)k.shadow);
+  }
+  for (auto& r : e.res_names) f.str(r);
+  for (uint64_t x : {(uint64_t)e.k_zone, (uint64_t)e.k_ct, (uint64_t)e.k_hostname, (uint64_t)e.k_nodepool, (uint64_t)e.k_dom,
+                     (uint64_t)e.dom_ct, (uint64_t)e.dom_np, (uint64_t)e.N, (uint64_t)e.W, (uint64_t)e.R, (uint64_t)e.Z,
+                     (uint64_t)e.C, (uint64_t)e.T, (uint64_t)e.F, (uint64_t)e.V, (uint64_t)e.P, (uint64_t)e.K,
+                     (uint64_t)e.NT, e.wk_slots, e.checks, e.checks_per_pod, (uint64_t)e.it_key_unique,
+                     (uint64_t)e.any_mv, (uint64_t)e.any_vol, (uint64_t)e.NN, (uint64_t)e.TG, (uint64_t)e.TGH,
+                     (uint64_t)e.TGZ, (uint64_t)e.NZV, (uint64_t)e.ZS, (uint64_t)e.n_lazy, e.known_np, e.zknown0})
+    f.u64(x);
+  for (auto& r : e.tmpl_reqs) f.str(gsh::canonical(e, r));
+  for (auto& v : e.variants) {
+    f.str(gsh::canonical(e, v.reqs));
+    f.str(gsh::canonical(e, v.strict));
+    f.u64(v.tol);
+    f.u64(v.own.size());
+    for (uint32_t g : v.own) f.u64(g);
+    f.u64(v.lazy_mind.size());
+    for (auto& lm : v.lazy_mind) f.u64(((uint64_t)lm.first << 32) | (uint32_t)lm.second);
+  }
+  printf("  host %zu %zu %016llx\n", e.tmpl_reqs.size(), e.variants.size(), (unsigned long long)f.h);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   int reps = 1, i = 1;
-  if (argc > 2 && strcmp(argv[1], "-n") == 0) {
-    reps = atoi(argv[2]);
-    i = 3;
+  bool dump = false;
+  for (; i < argc && argv[i][0] == '-'; i++) {
+    if (strcmp(argv[i], "-d") == 0) dump = true;
+    else if (strcmp(argv[i], "-n") == 0 && i + 1 < argc) reps = atoi(argv[++i]);
+    else break;
   }
   int rc = 0;
   for (; i < argc; i++) {
@@ -107,6 +176,7 @@ int main(int argc, char** argv) {
       if (ms < best) best = ms;
     }
     printf("%d %.3f %s\n", (int)er.code, best, argv[i]);
+    if (dump) digest(er, e);
   }
   return rc;
 }
