@@ -566,6 +566,45 @@ gs_status gs_batch_last_run(const gs_ctx* ctx, gs_batch_stats* out);
 /* sizeof the stats struct, for a binding's layout check */
 uint32_t gs_batch_stats_size(void);
 
+/* ---- a batch of independent consolidations: several clusters, one device ---
+ * The disruption half of the same fleet: every input of a batch has its own
+ * cluster, candidates, mode, max_candidates and shard filter, and its outcome
+ * is the one gs_consolidate gives for it alone.  The simulations of all slots
+ * run side by side in a number of device operations (kernel launches, memsets
+ * and copies together) that depends on the number of kernel instantiations
+ * among them, not on how many slots there are.  The batch is separate from
+ * the Solve batch, from the context's single prepared problem and from a
+ * resident gs_consolidate: none disturbs another.  The stats reuse
+ * gs_batch_stats: n_batched / n_fallback count accepted slots the batched
+ * launches did or did not cover (a slot without simulations needs no launch
+ * and counts as batched), n_launches counts every device operation of the
+ * run. */
+/* check + encode + plan + upload each input; status[i] receives input i's own
+ * gs_status.  A refused, invalid or over-capacity input fails neither the call
+ * nor the other slots.  Returns GS_OK unless the call itself is invalid (NULL
+ * arguments, GS_E_CAPACITY for n over GS_BATCH_MAX, a context with shards) or
+ * HIP fails.  n = 0 is valid.  A second call replaces the first batch; the
+ * caller's arrays are not kept. */
+gs_status gs_batch_consolidate_prepare(gs_ctx* ctx, const gs_consolidation* const* in, uint32_t n, gs_status* status);
+/* the device part of every accepted slot (commands are decided by the fetch);
+ * can be called repeatedly */
+gs_status gs_batch_consolidate_run(gs_ctx* ctx);
+/* copy slot i's outcome back and decide it: exactly what gs_consolidate of that
+ * input alone returns, with t_feas_ms / t_sim_ms / t_truncate_ms 0 for a slot
+ * the batched launches covered (the batch's times are in the stats), or slot
+ * i's status when it was refused.  A slot whose simulation fails fails only
+ * its own fetch.  Valid until the next batch prepare or run, or gs_destroy. */
+gs_status gs_batch_consolidate_fetch(gs_ctx* ctx, uint32_t i, gs_consolidation_result* out);
+/* gs_consolidation_results for slot i: simulation `sim` runs again alone on the
+ * slot's resident upload.  A following fetch and a following run return the
+ * same commands.  GS_E_INVALID: the batch has not run, sim >= n_commands, or
+ * the command is GS_DECISION_SKIPPED. */
+gs_status gs_batch_consolidate_results(gs_ctx* ctx, uint32_t i, uint32_t sim, gs_result* out);
+/* slot i's message (why its input was refused, or why its fetch failed) */
+size_t gs_batch_consolidate_error(const gs_ctx* ctx, uint32_t i, char* buf, size_t len);
+/* counters and times of the last consolidation batch prepare / run */
+gs_status gs_batch_consolidate_last_run(const gs_ctx* ctx, gs_batch_stats* out);
+
 /* static feasibility matrix only (K1/K2) on a prepared problem */
 gs_status gs_feasibility(gs_ctx* ctx, gs_feas_result* out);
 /* one instance-type column shard of it: only words

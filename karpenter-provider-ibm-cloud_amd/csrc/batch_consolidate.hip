@@ -1,0 +1,398 @@
+// batch_consolidate.hip — gs_batch_consolidate_*: the consolidation
+// simulations of many independent clusters on one context, in a number of
+// device operations that does not depend on how many clusters they are.
+//
+// A slot is a child gs_ctx as in batch.cpp (it borrows the parent's stream
+// and events) holding what gs_consolidate leaves resident: the input copy,
+// the encoding, the plan, the arena and the pinned result staging.  Prepare
+// runs gs_consolidate's host steps per slot (consolidate.cpp cons_*: check,
+// take + encode and plan the sets on up to 16 host threads, then the grid plan
+// and the upload one after another), copies the DevProblem structs of the
+// slots with simulations into one device array ordered by group, followed by
+// each slot's workgroup count, and that is the only copy: a run launches
+// kernels only.
+//
+//  group     the slots that need the same instantiation of every kernel:
+//            (R, general or not) of the simulation kernel, the lane-pair width
+//            of K1/K2, and whether K3 runs the minValues form.  The shape
+//            (FB_SIM / FB_SIM_NARROW) is one per batch, from the total number
+//            of simulations.  Five launches per group (six with minValues):
+//            cursors, rows, begin (work counters; overlay cells when the
+//            stamp prefix wraps), simulations, truncation (+ settlement).
+//  no launch a slot without simulations (no candidates, or all filtered by its
+//            shard filter): its fetch decides an empty or all-SKIPPED table.
+//  fallback  a slot whose simulations need more dynamic LDS than the batched
+//            instantiations may use: cons_launch on the slot after the
+//            batched launches.  The single kernel has the same static LDS, so
+//            none is expected; the path keeps such a slot correct.
+//  epoch     the overlay stamp prefix is the batch's and travels as a kernel
+//            argument, so a run copies nothing; gs_batch_consolidate_results
+//            draws the next prefix for its rerun, and when the prefix wraps
+//            every group's overlay cells are cleared (one launch per group).
+#include <atomic>
+#include <thread>
+#include <tuple>
+
+#include "ctx.hpp"
+
+namespace gsc {
+
+struct ConsSlot {
+  gs_ctx* c = nullptr;
+  gs_status status = GS_E_INVALID;
+  bool grouped = false;   // in the device array: the batched launches cover it
+  bool fallback = false;  // has simulations the batched launches do not cover
+  bool fetched = false;   // copied back and decided since the last run
+  gs_status fetch_status = GS_OK;
+};
+
+struct ConsBatch {
+  std::vector<ConsSlot> slots;  // only grows: a slot's arena and pinned staging are reused
+  uint32_t n = 0;               // slots of the current batch
+  bool prepared = false, ran = false;
+  uint32_t nt = 256;            // the batch's simulation workgroup shape
+  uint32_t epoch = 0;           // the last overlay stamp prefix drawn (1..4095)
+  struct Group {
+    uint32_t R, general, lp, mv;
+    uint32_t first = 0, count = 0;  // range of the device array
+    uint32_t lds = 0, max_blocks = 0, max_sims = 0, max_slots = 0, trunc_lds = 0;
+    uint64_t max_cursors = 0, max_pairs = 0;
+  };
+  std::vector<Group> groups;
+  std::vector<uint32_t> order;  // device array position -> slot
+  // the device image: order.size() DevProblem, then order.size() workgroup counts
+  void* dev = nullptr;
+  size_t dev_cap = 0;
+  const gsd::DevProblem* problems() const { return (const gsd::DevProblem*)dev; }
+  const uint32_t* blocks() const { return (const uint32_t*)((const char*)dev + order.size() * sizeof(gsd::DevProblem)); }
+  gs_batch_stats stats{};
+};
+
+namespace {
+
+constexpr uint32_t kEncodeThreads = 16;
+using GroupKey = std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>;
+
+void free_slot(gs_ctx* s) {
+  s->free_all();
+  if (s->arena) (void)hipFree(s->arena);
+  if (s->stage) (void)hipHostFree(s->stage);
+  delete s;  // the stream and the events are the parent's
+}
+
+GroupKey key_of(const gsh::Encoded& e) {
+  const uint32_t general = (e.TG || e.any_mv || e.any_vol) ? 1u : 0u;
+  return GroupKey{e.R, general, gsk_feas_lp(e.W), e.any_mv ? 1u : 0u};
+}
+
+// the dynamic LDS gsk_ffd requests for a problem's simulations
+uint32_t sim_lds(const gsd::DevProblem& d) {
+  return gsk_ffd_lds_bytes(d.max_claims, d.n_thr, d.nb_words, gsd::topo_lds_bytes(d.TGZ, d.ZS, d.TGH, d.n_lazy)) +
+         8u * d.ovh_slots + (d.sim_lds ? 32u * d.max_claims : 0u);
+}
+
+bool eligible(const ConsBatch& b, const ConsSlot& s) {
+  const gsd::DevProblem& d = s.c->dp;
+  return d.R >= 1 && d.R <= 8 && d.sim_nt == b.nt && sim_lds(d) <= gsk_ffd_sim_batch_dyn_lds_max();
+}
+
+// the device array of the slots with simulations, ordered by group, and their
+// workgroup counts: one copy
+void build_groups(gs_ctx* c, ConsBatch& b) {
+  std::map<GroupKey, std::vector<uint32_t>> by;
+  for (uint32_t i = 0; i < b.n; i++) {
+    ConsSlot& s = b.slots[i];
+    s.grouped = s.fallback = false;
+    if (s.status != GS_OK || s.c->sims.evaluated.empty()) continue;
+    if (eligible(b, s)) by[key_of(s.c->enc)].push_back(i);
+    else s.fallback = true;
+  }
+  b.groups.clear();
+  b.order.clear();
+  std::vector<gsd::DevProblem> problems;
+  std::vector<uint32_t> blocks;
+  for (auto& kv : by) {
+    ConsBatch::Group g{};
+    std::tie(g.R, g.general, g.lp, g.mv) = kv.first;
+    g.first = (uint32_t)b.order.size();
+    g.count = (uint32_t)kv.second.size();
+    for (uint32_t i : kv.second) {
+      ConsSlot& s = b.slots[i];
+      const gsd::DevProblem& d = s.c->dp;
+      const SimPlan& sp = s.c->sims;
+      g.lds = std::max(g.lds, sim_lds(d));
+      g.max_blocks = std::max(g.max_blocks, sp.blocks);
+      g.max_sims = std::max(g.max_sims, d.n_sims);
+      g.max_slots = std::max(g.max_slots, (uint32_t)sp.pods.size());
+      g.trunc_lds = std::max(g.trunc_lds, trunc_lds_bytes(d.N));
+      g.max_pairs = std::max<uint64_t>(g.max_pairs, (uint64_t)d.V * d.T);
+      g.max_cursors = std::max<uint64_t>(g.max_cursors, (uint64_t)d.V * d.T * d.R);
+      s.grouped = true;
+      b.order.push_back(i);
+      problems.push_back(d);
+      blocks.push_back(sp.blocks);
+    }
+    b.groups.push_back(g);
+  }
+  const size_t n = b.order.size(), bytes = n * (sizeof(gsd::DevProblem) + sizeof(uint32_t));
+  if (!n) return;
+  if (bytes > b.dev_cap) {
+    if (b.dev) HIPCHK(hipFree(b.dev));
+    b.dev = nullptr;
+    b.dev_cap = 0;
+    const size_t want = bytes + bytes / 4;
+    HIPCHK(hipMalloc(&b.dev, want));
+    b.dev_cap = want;
+  }
+  std::vector<char> image(bytes);
+  std::memcpy(image.data(), problems.data(), n * sizeof(gsd::DevProblem));
+  std::memcpy(image.data() + n * sizeof(gsd::DevProblem), blocks.data(), n * sizeof(uint32_t));
+  HIPCHK(hipMemcpyAsync(b.dev, image.data(), bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+}
+
+// the next overlay stamp prefix (next_overlay_epoch's rule for the batch);
+// true when it wrapped: the cells of 4,095 launches ago could match again, so
+// every group's are cleared before the prefix is used
+bool next_epoch(ConsBatch& b) {
+  b.epoch = (b.epoch + 1u) & 0xFFFu;
+  if (b.epoch) return false;
+  b.epoch = 1;
+  return true;
+}
+
+gs_status fetch_slot(gs_ctx* c, ConsSlot& s, gs_consolidation_result* out) {
+  if (!s.fetched) {
+    if (hipSetDevice(c->device) != hipSuccess) return fail(s.c, GS_E_HIP, "hipSetDevice failed");
+    s.fetch_status = cons_fetch_decide(s.c, out);
+    s.fetched = true;
+    return s.fetch_status;
+  }
+  if (s.fetch_status == GS_OK) cons_fill_result(s.c, out);
+  return s.fetch_status;
+}
+
+}  // namespace
+
+void batch_consolidate_destroy(gs_ctx* c) {
+  ConsBatch* b = c->cons_batch;
+  if (!b) return;
+  for (auto& s : b->slots)
+    if (s.c) free_slot(s.c);
+  if (b->dev) (void)hipFree(b->dev);
+  delete b;
+  c->cons_batch = nullptr;
+}
+
+}  // namespace gsc
+
+using namespace gsc;
+
+extern "C" {
+
+gs_status gs_batch_consolidate_prepare(gs_ctx* c, const gs_consolidation* const* in, uint32_t n, gs_status* status) {
+  if (!c) return GS_E_INVALID;
+  if (n && (!in || !status)) return fail(c, GS_E_INVALID, "gs_batch_consolidate_prepare: NULL inputs or status");
+  if (!c->shards.empty())
+    return fail(c, GS_E_INVALID, "gs_batch_consolidate_prepare: a context with shards runs no batch");
+  if (n > GS_BATCH_MAX) return fail(c, GS_E_CAPACITY, "gs_batch_consolidate_prepare: more than 4096 inputs");
+  const auto t0 = Clock::now();
+  if (!c->cons_batch) c->cons_batch = new ConsBatch();
+  ConsBatch& b = *c->cons_batch;
+  b.prepared = b.ran = false;
+  b.n = 0;
+  b.groups.clear();
+  b.order.clear();
+  while (b.slots.size() < n) {
+    ConsSlot s;
+    s.c = new gs_ctx();
+    s.c->device = c->device;
+    s.c->cfg_flags = c->cfg_flags;
+    s.c->stream = c->stream;
+    std::copy(std::begin(c->ev), std::end(c->ev), std::begin(s.c->ev));
+    b.slots.push_back(s);
+  }
+  // check, take + encode and plan the sets on up to 16 host threads (the
+  // encoder's own loops share its pool)
+  std::atomic<uint32_t> next{0};
+  auto work = [&] {
+    for (;;) {
+      const uint32_t i = next.fetch_add(1);
+      if (i >= n) return;
+      ConsSlot& s = b.slots[i];
+      gs_ctx* sc = s.c;
+      sc->prepared = sc->ran = false;
+      sc->cons_ready = false;
+      sc->err.clear();
+      sc->sims = SimPlan{};
+      sc->commands.clear();
+      s.grouped = s.fallback = s.fetched = false;
+      s.fetch_status = GS_OK;
+      std::string err;
+      s.status = cons_check_input(in[i], &err);
+      if (s.status != GS_OK) {
+        fail(sc, s.status, err);
+        continue;
+      }
+      s.status = cons_take_input(sc, in[i]);
+      if (s.status != GS_OK) continue;
+      s.status = cons_plan_sets(sc, &err);
+      if (s.status != GS_OK) fail(sc, s.status, err);
+    }
+  };
+  {
+    std::vector<std::thread> th;
+    const uint32_t nt = std::min<uint32_t>(kEncodeThreads, n);
+    for (uint32_t t = 1; t < nt; t++) th.emplace_back(work);
+    work();
+    for (auto& t : th) t.join();
+  }
+  // the batch's shape from all its simulations, each slot's share of its
+  // group's resident workgroups, then the uploads and the device array
+  uint32_t accepted = 0;
+  try {
+    HIPCHK(hipSetDevice(c->device));
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
+    size_t total = 0;
+    std::map<GroupKey, uint64_t> group_sims;
+    for (uint32_t i = 0; i < n; i++) {
+      const ConsSlot& s = b.slots[i];
+      if (s.status != GS_OK) continue;
+      total += s.c->sims.evaluated.size();
+      group_sims[key_of(s.c->enc)] += s.c->sims.evaluated.size();
+    }
+    b.nt = cons_sim_threads(total, cus);
+    for (uint32_t i = 0; i < n; i++) {
+      ConsSlot& s = b.slots[i];
+      if (s.status != GS_OK) continue;
+      std::string err;
+      const SimBudget budget{b.nt, group_sims[key_of(s.c->enc)]};
+      s.status = cons_plan_grid(s.c, &budget, &err);
+      if (s.status != GS_OK) {
+        fail(s.c, s.status, err);
+        continue;
+      }
+      const gs_status up = cons_upload(s.c);
+      if (up != GS_OK) throw HipError{"slot " + std::to_string(i) + ": " + s.c->err};
+      accepted++;
+    }
+    b.n = n;
+    build_groups(c, b);
+  } catch (const HipError& e) {
+    for (uint32_t i = 0; i < n; i++) status[i] = b.slots[i].status;
+    return fail(c, GS_E_HIP, e.msg);
+  }
+  for (uint32_t i = 0; i < n; i++) status[i] = b.slots[i].status;
+  b.prepared = true;
+  b.stats = gs_batch_stats{};
+  b.stats.n_problems = n;
+  b.stats.n_accepted = accepted;
+  b.stats.prepare_ms = ms_since(t0);
+  return GS_OK;
+}
+
+gs_status gs_batch_consolidate_run(gs_ctx* c) {
+  if (!c || !c->cons_batch || !c->cons_batch->prepared) return GS_E_INVALID;
+  ConsBatch& b = *c->cons_batch;
+  const auto tw = Clock::now();
+  uint32_t launches = 0, n_batched = 0, n_fallback = 0;
+  float dev_ms = 0;
+  b.ran = false;
+  try {
+    HIPCHK(hipSetDevice(c->device));
+    if (!b.groups.empty()) {
+      const uint32_t wrapped = next_epoch(b) ? 1u : 0u;
+      HIPCHK(hipEventRecord(c->ev[6], c->stream));
+      for (const ConsBatch::Group& g : b.groups) {
+        const gsd::DevProblem* ds = b.problems() + g.first;
+        const uint32_t* blk = b.blocks() + g.first;
+        HIPCHK(gsk_feas_batch(ds, g.count, g.lp, g.max_cursors, g.max_pairs, c->stream));
+        HIPCHK(gsk_sim_begin_batch(ds, blk, g.count, wrapped, c->stream));
+        HIPCHK(gsk_ffd_sim_batch(ds, blk, g.count, g.max_blocks, g.R, g.general, b.nt, g.lds, b.epoch, c->stream));
+        HIPCHK(gsk_trunc_sims_batch(ds, g.count, g.mv, g.max_sims, g.max_slots, g.trunc_lds, c->stream));
+        launches += g.mv ? 6u : 5u;
+      }
+      HIPCHK(hipEventRecord(c->ev[7], c->stream));
+      HIPCHK(hipEventSynchronize(c->ev[7]));
+      HIPCHK(hipEventElapsedTime(&dev_ms, c->ev[6], c->ev[7]));
+    }
+  } catch (const HipError& e) {
+    for (uint32_t i : b.order) reset_sim_counts(b.slots[i].c);
+    return fail(c, GS_E_HIP, e.msg);
+  }
+  for (uint32_t i = 0; i < b.n; i++) {
+    ConsSlot& s = b.slots[i];
+    if (s.status != GS_OK) continue;
+    gs_ctx* sc = s.c;
+    s.fetched = false;
+    s.fetch_status = GS_OK;
+    if (s.fallback) {
+      const gs_status st = cons_launch(sc);
+      if (st != GS_OK) return fail(c, st, "slot " + std::to_string(i) + ": " + sc->err);
+      n_fallback++;
+      continue;
+    }
+    // covered by the batched launches, or without simulations (no launch)
+    sc->t_feas = sc->t_sim = sc->t_trunc = 0;
+    if (s.grouped) sc->dp.ov_epoch = b.epoch;
+    n_batched++;
+  }
+  b.ran = true;
+  b.stats.n_batched = n_batched;
+  b.stats.n_fallback = n_fallback;
+  b.stats.n_groups = (uint32_t)b.groups.size();
+  b.stats.n_launches = launches;
+  b.stats.device_ms = dev_ms;
+  b.stats.run_ms = ms_since(tw);
+  return GS_OK;
+}
+
+gs_status gs_batch_consolidate_fetch(gs_ctx* c, uint32_t i, gs_consolidation_result* out) {
+  if (!c || !out || !c->cons_batch || !c->cons_batch->prepared || i >= c->cons_batch->n) return GS_E_INVALID;
+  ConsSlot& s = c->cons_batch->slots[i];
+  if (s.status != GS_OK) return s.status;
+  if (!c->cons_batch->ran) return GS_E_INVALID;
+  return fetch_slot(c, s, out);
+}
+
+gs_status gs_batch_consolidate_results(gs_ctx* c, uint32_t i, uint32_t sim, gs_result* out) {
+  if (!c || !out || !c->cons_batch || !c->cons_batch->prepared || i >= c->cons_batch->n) return GS_E_INVALID;
+  ConsBatch& b = *c->cons_batch;
+  ConsSlot& s = b.slots[i];
+  if (s.status != GS_OK) return s.status;
+  if (!b.ran) return GS_E_INVALID;
+  // the rerun overwrites what the fetch copies back: decide the slot first
+  gs_consolidation_result table;
+  const gs_status fs = fetch_slot(c, s, &table);
+  if (fs != GS_OK) return fs;
+  gs_ctx* sc = s.c;
+  if (sim >= sc->commands.size()) return fail(sc, GS_E_INVALID, "simulation index out of range");
+  if (sc->commands[sim].decision == GS_DECISION_SKIPPED)
+    return fail(sc, GS_E_INVALID, "simulation skipped by the shard filter");
+  if (s.grouped) {
+    try {
+      HIPCHK(hipSetDevice(c->device));
+      if (next_epoch(b))
+        for (const ConsBatch::Group& g : b.groups)
+          HIPCHK(gsk_sim_begin_batch(b.problems() + g.first, b.blocks() + g.first, g.count, 1u, c->stream));
+    } catch (const HipError& e) {
+      return fail(sc, GS_E_HIP, e.msg);
+    }
+    sc->dp.ov_epoch = b.epoch - 1u;  // cons_sim_results draws the next one: the batch's
+  }
+  return cons_sim_results(sc, sim, out);
+}
+
+size_t gs_batch_consolidate_error(const gs_ctx* c, uint32_t i, char* buf, size_t len) {
+  if (!c || !c->cons_batch || i >= c->cons_batch->n) return 0;
+  return gs_last_error(c->cons_batch->slots[i].c, buf, len);
+}
+
+gs_status gs_batch_consolidate_last_run(const gs_ctx* c, gs_batch_stats* out) {
+  if (!c || !out || !c->cons_batch || !c->cons_batch->prepared) return GS_E_INVALID;
+  *out = c->cons_batch->stats;
+  return GS_OK;
+}
+
+}  // extern "C"

@@ -592,6 +592,7 @@ gs_status gs_create(const gs_config* cfg, gs_ctx** out) {
     HIPCHK(gsk_init_trunc(65536));
     HIPCHK(gsk_init_batch(65536));
     HIPCHK(gsk_init_ffdw_batch(kLdsBytes));
+    HIPCHK(gsk_init_ffd_sim_batch(kLdsBytes));
   } catch (const HipError& e) {
     delete c;
     return GS_E_HIP;
@@ -648,6 +649,7 @@ void gs_destroy(gs_ctx* c) {
   c->shards.clear();
   (void)hipSetDevice(c->device);
   batch_destroy(c);
+  batch_consolidate_destroy(c);
   c->free_all();
   if (c->arena) (void)hipFree(c->arena);
   if (c->stage) (void)hipHostFree(c->stage);

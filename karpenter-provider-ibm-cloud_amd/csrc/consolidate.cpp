@@ -250,8 +250,11 @@ int32_t choose(const CandTable& t, uint32_t mode, const std::vector<std::vector<
   return chosen;
 }
 
-// pods of each evaluated simulation in queue order, node positions removed
-gs_status plan_sims(gs_ctx* c, const gs_consolidation* in, std::string* err) {
+}  // namespace
+
+// step 2 (a): pods of each evaluated simulation in queue order, node positions removed
+gs_status cons_plan_sets(gs_ctx* c, std::string* err) {
+  const gs_consolidation* in = &c->cons_in;
   SimPlan& sp = c->sims;
   const gsh::Encoded& e = c->enc;
   gs_status st = build_sets(in, sp, err);
@@ -316,6 +319,17 @@ gs_status plan_sims(gs_ctx* c, const gs_consolidation* in, std::string* err) {
     *err = "a simulation holds more than 65535 pods";
     return GS_E_CAPACITY;
   }
+  return GS_OK;
+}
+
+// step 2 (b): the simulation kernel's shape, the persistent workgroups and
+// what follows their count.  budget null: the device is this problem's alone.
+// A batch slot (batch_consolidate.hip) is given its batch's shape and takes
+// its share, by simulations, of the workgroups its group keeps resident: at
+// least one, never more than it has simulations.
+gs_status cons_plan_grid(gs_ctx* c, const SimBudget* budget, std::string* err) {
+  SimPlan& sp = c->sims;
+  const gsh::Encoded& e = c->enc;
   const uint32_t lds = gsk_ffd_lds_bytes(std::max<uint32_t>(sp.max_pods, 1), (uint32_t)e.thr_val.size(),
                                          (e.NN + 31) / 32, gsd::topo_lds_bytes(e.TGZ, e.ZS, e.TGH, e.n_lazy)) +
                        8u * gsd::ovh_slots_for(sp.ov_cap);
@@ -329,14 +343,15 @@ gs_status plan_sims(gs_ctx* c, const gs_consolidation* in, std::string* err) {
   // resident (occupancy of the simulation kernel at this LDS size)
   // many simulations: the narrow workgroup (throughput); few: the wide one
   // (each simulation's latency) -- ffd.hip FB_SIM / FB_SIM_NARROW
-  sp.nt = sp.evaluated.size() >= 4 * (size_t)std::max(cus, 1) ? 128u : 256u;
+  sp.nt = budget ? budget->nt : cons_sim_threads(sp.evaluated.size(), cus);
   const bool general = e.TG || e.any_mv || e.any_vol;
-  uint32_t per_cu = gsk_ffd_sim_blocks_per_cu(e.R, lds, sp.nt, general ? 1u : 0u);
+  auto occupancy = budget ? gsk_ffd_sim_batch_blocks_per_cu : gsk_ffd_sim_blocks_per_cu;
+  uint32_t per_cu = occupancy(e.R, lds, sp.nt, general ? 1u : 0u);
   // the simulations' queue arrays and add logs in LDS when that costs no
   // resident workgroup (ffd.hip s_simq / s_simlog)
   const uint32_t lds_q = lds + 32u * std::max<uint32_t>(sp.max_pods, 1);
   sp.sim_lds = false;
-  if (lds_q <= gsk_ffd_dyn_lds_max() && gsk_ffd_sim_blocks_per_cu(e.R, lds_q, sp.nt, general ? 1u : 0u) >= per_cu) {
+  if (lds_q <= gsk_ffd_dyn_lds_max() && occupancy(e.R, lds_q, sp.nt, general ? 1u : 0u) >= per_cu) {
     sp.sim_lds = true;
   }
   if (const char* x = std::getenv("GS_SIM_LDS"))  // A/B experiments: 0 off, 1 on whenever it fits
@@ -344,17 +359,30 @@ gs_status plan_sims(gs_ctx* c, const gs_consolidation* in, std::string* err) {
   if (std::getenv("GS_SIM_DEBUG"))
     std::fprintf(stderr, "gpusched sim plan: sims %zu max_pods %u nt %u lds %u per_cu %u lds_q per_cu %u sim_lds %d\n",
                  sp.evaluated.size(), sp.max_pods, sp.nt, lds, per_cu,
-                 gsk_ffd_sim_blocks_per_cu(e.R, lds_q, sp.nt, general ? 1u : 0u), (int)sp.sim_lds);
+                 occupancy(e.R, lds_q, sp.nt, general ? 1u : 0u), (int)sp.sim_lds);
   if (const char* x = std::getenv("GS_SIM_PER_CU"))  // experiments: fewer persistent workgroups per CU
     per_cu = std::max<uint32_t>(1, std::min<uint32_t>(per_cu, (uint32_t)std::atoi(x)));
   sp.blocks = (uint32_t)std::min<size_t>(sp.evaluated.size(), (size_t)std::max(cus, 1) * per_cu);
+  if (budget && !sp.evaluated.empty()) {
+    const uint64_t resident = (uint64_t)std::max(cus, 1) * per_cu;
+    const uint64_t share = resident * sp.evaluated.size() / std::max<uint64_t>(budget->group_sims, sp.evaluated.size());
+    sp.blocks = (uint32_t)std::min<uint64_t>(sp.evaluated.size(), std::max<uint64_t>(share, 1));
+  }
   // per-block overlays of hostname counts: at most 1 GiB (fewer persistent blocks otherwise)
   const size_t ov_row = (size_t)std::max<uint32_t>(sp.ov_cap, 1) * e.TGH * sizeof(uint64_t);
   if (ov_row) sp.blocks = (uint32_t)std::max<size_t>(1, std::min<size_t>(sp.blocks, (size_t)(1u << 30) / ov_row));
   return GS_OK;
 }
 
-// launch the device part and decide every evaluated simulation
+namespace {
+
+gs_status plan_sims(gs_ctx* c, std::string* err) {
+  const gs_status st = cons_plan_sets(c, err);
+  return st != GS_OK ? st : cons_plan_grid(c, nullptr, err);
+}
+
+}  // namespace
+
 // A simulation clears the NodeClaim hostname-count cells it recorded at its
 // own end (ffd.hip: the rows stay zero at rest).  A launch that failed, or a
 // simulation that stopped early, may leave cells set: clear the rows so a
@@ -377,16 +405,12 @@ void next_overlay_epoch(gs_ctx* c) {
   }
 }
 
-gs_status run_and_decide(gs_ctx* c, gs_consolidation_result* out) {
-  const gsh::Encoded& e = c->enc;
+// step 4: the device part of every evaluated simulation (K1/K2, the
+// simulation kernel, K3), timed
+gs_status cons_launch(gs_ctx* c) {
   const SimPlan& sp = c->sims;
-  const gs_consolidation* in = &c->cons_in;
   auto& d = c->dp;
   const size_t NS = sp.evaluated.size();
-  const gsd::SimCtrl* ctrl = c->h_ctrl;
-  const gsd::ClaimRec* hdr = c->h_hdr;
-  const uint32_t* its = c->h_its;
-  const uint32_t* nits = c->h_nits;
   float a = 0, b = 0, x = 0;
   try {
     HIPCHK(hipSetDevice(c->device));
@@ -412,6 +436,21 @@ gs_status run_and_decide(gs_ctx* c, gs_consolidation_result* out) {
   c->t_feas = a;
   c->t_sim = b;
   c->t_trunc = x;
+  return GS_OK;
+}
+
+// step 5: copy every evaluated simulation's outcome back and decide it
+// (computeConsolidation per simulation, then the mode's policy)
+gs_status cons_fetch_decide(gs_ctx* c, gs_consolidation_result* out) {
+  const gsh::Encoded& e = c->enc;
+  const SimPlan& sp = c->sims;
+  const gs_consolidation* in = &c->cons_in;
+  auto& d = c->dp;
+  const size_t NS = sp.evaluated.size();
+  const gsd::SimCtrl* ctrl = c->h_ctrl;
+  const gsd::ClaimRec* hdr = c->h_hdr;
+  const uint32_t* its = c->h_its;
+  const uint32_t* nits = c->h_nits;
   auto t0 = Clock::now();
   try {
     if (NS) {
@@ -546,27 +585,46 @@ gs_status run_and_decide(gs_ctx* c, gs_consolidation_result* out) {
     chosen = choose(c->cand_table, in->mode, sp.sets, sp.multi_max, c->commands.data(), c->cmd_options.data(),
                     c->cmd_prices.data(), &c->multi_opts);
   c->t_fetch = ms_since(t0);
+  c->cons_chosen = chosen;
+  c->cons_checks = checks;
+  c->cons_node_evals = node_evals;
+  c->cons_node_prefix = node_prefix;
+  c->cons_pops = pops;
+  cons_fill_result(c, out);
+  return GS_OK;
+}
+
+// the decided table of the last cons_fetch_decide
+void cons_fill_result(const gs_ctx* c, gs_consolidation_result* out) {
   std::memset(out, 0, sizeof(*out));
   out->n_commands = (uint32_t)c->commands.size();
   out->commands = c->commands.data();
   out->options = c->cmd_options.data();
   out->option_prices = c->cmd_prices.data();
-  out->chosen = chosen;
+  out->chosen = c->cons_chosen;
   out->n_multi_options = (uint32_t)c->multi_opts.size();
   out->multi_options = c->multi_opts.data();
-  out->pods_simulated = (uint32_t)sp.pods.size();
-  out->checks = checks;
-  out->node_evals = node_evals;
-  out->node_prefix = node_prefix;
-  out->pops = pops;
+  out->pods_simulated = (uint32_t)c->sims.pods.size();
+  out->checks = c->cons_checks;
+  out->node_evals = c->cons_node_evals;
+  out->node_prefix = c->cons_node_prefix;
+  out->pops = c->cons_pops;
   out->t_encode_ms = c->t_encode;
   out->t_upload_ms = c->t_upload;
   out->t_feas_ms = c->t_feas;
   out->t_sim_ms = c->t_sim;
   out->t_truncate_ms = c->t_trunc;
   out->t_fetch_ms = c->t_fetch;
-  return GS_OK;
 }
+
+namespace {
+
+gs_status run_and_decide(gs_ctx* c, gs_consolidation_result* out) {
+  const gs_status st = cons_launch(c);
+  return st != GS_OK ? st : cons_fetch_decide(c, out);
+}
+
+}  // namespace
 
 // <U> SimulateScheduling's scheduling.Results of evaluated simulation k.  The
 // sweep keeps one SimCtrl, one header and one top 60 per simulation (with
@@ -576,7 +634,7 @@ gs_status run_and_decide(gs_ctx* c, gs_consolidation_result* out) {
 // Truncate(60) of every NodeClaim it opened.  The decode is gs_fetch's; pod
 // ids are the combined list's (pending i, bound b -> n_pending + b), which the
 // kernel's records already carry.  Nothing the commands point into is touched.
-gs_status sim_results(gs_ctx* c, uint32_t sim, gs_result* out) {
+gs_status cons_sim_results(gs_ctx* c, uint32_t sim, gs_result* out) {
   const gsh::Encoded& e = c->enc;
   const SimPlan& sp = c->sims;
   const auto at = std::lower_bound(sp.evaluated.begin(), sp.evaluated.end(), sim);
@@ -666,7 +724,7 @@ gs_status sim_results(gs_ctx* c, uint32_t sim, gs_result* out) {
   return GS_OK;
 }
 
-gs_status check_input(const gs_consolidation* in, std::string* err) {
+gs_status cons_check_input(const gs_consolidation* in, std::string* err) {
   if (!in || !in->cluster) {
     *err = "null input";
     return GS_E_INVALID;
@@ -693,29 +751,9 @@ gs_status check_input(const gs_consolidation* in, std::string* err) {
   return GS_OK;
 }
 
-}  // namespace
-
-// the host policy replay over a complete command table (gs_consolidation_choose
-// and the sharded context's merge)
-int32_t choose_commands(const CandTable& t, const gs_consolidation* in, const gs_command* commands,
-                        const uint32_t* options, const double* prices, std::vector<uint32_t>* multi) {
-  SimPlan sp;
-  std::string err;
-  if (build_sets(in, sp, &err) != GS_OK) return -1;
-  return choose(t, in->mode, sp.sets, sp.multi_max, commands, options, prices, multi);
-}
-}  // namespace gsc
-
-using namespace gsc;
-
-extern "C" {
-
-gs_status gs_consolidate(gs_ctx* c, const gs_consolidation* in, gs_consolidation_result* out) {
-  if (!c || !out) return GS_E_INVALID;
-  std::string err;
-  gs_status st = check_input(in, &err);
-  if (st != GS_OK) return fail(c, st, err);
-  if (!c->shards.empty()) return sharded_consolidate(c, in, out);
+// step 1: take a checked input (own copies of what the decisions and a rerun
+// read from the caller's memory) and encode its combined problem
+gs_status cons_take_input(gs_ctx* c, const gs_consolidation* in) {
   c->prepared = c->ran = false;
   c->cons_ready = false;  // until this input is resident
   // own copies of the caller's candidate arrays (gs_consolidate_rerun)
@@ -743,8 +781,12 @@ gs_status gs_consolidate(gs_ctx* c, const gs_consolidation* in, gs_consolidation
   if (er.code != GS_OK) return fail(c, er.code, er.msg);
   er = capacity_check(c->enc);
   if (er.code != GS_OK) return fail(c, er.code, er.msg);
-  st = plan_sims(c, &c->cons_in, &err);
-  if (st != GS_OK) return fail(c, st, err);
+  return GS_OK;
+}
+
+// step 3: the encoding and the plan into the device arena; the input is
+// resident afterwards
+gs_status cons_upload(gs_ctx* c) {
   try {
     HIPCHK(hipSetDevice(c->device));
     auto t1 = Clock::now();
@@ -754,6 +796,36 @@ gs_status gs_consolidate(gs_ctx* c, const gs_consolidation* in, gs_consolidation
     return fail(c, GS_E_HIP, ex.msg);
   }
   c->cons_ready = true;
+  return GS_OK;
+}
+
+// the host policy replay over a complete command table (gs_consolidation_choose
+// and the sharded context's merge)
+int32_t choose_commands(const CandTable& t, const gs_consolidation* in, const gs_command* commands,
+                        const uint32_t* options, const double* prices, std::vector<uint32_t>* multi) {
+  SimPlan sp;
+  std::string err;
+  if (build_sets(in, sp, &err) != GS_OK) return -1;
+  return choose(t, in->mode, sp.sets, sp.multi_max, commands, options, prices, multi);
+}
+}  // namespace gsc
+
+using namespace gsc;
+
+extern "C" {
+
+gs_status gs_consolidate(gs_ctx* c, const gs_consolidation* in, gs_consolidation_result* out) {
+  if (!c || !out) return GS_E_INVALID;
+  std::string err;
+  gs_status st = cons_check_input(in, &err);
+  if (st != GS_OK) return fail(c, st, err);
+  if (!c->shards.empty()) return sharded_consolidate(c, in, out);
+  st = cons_take_input(c, in);
+  if (st != GS_OK) return st;
+  st = plan_sims(c, &err);
+  if (st != GS_OK) return fail(c, st, err);
+  st = cons_upload(c);
+  if (st != GS_OK) return st;
   return run_and_decide(c, out);
 }
 
@@ -770,14 +842,14 @@ gs_status gs_consolidation_results(gs_ctx* c, uint32_t sim, gs_result* out) {
   if (c->commands[sim].decision == GS_DECISION_SKIPPED)
     return fail(c, GS_E_INVALID, "simulation skipped by the shard filter");
   if (!c->shards.empty()) return sharded_results(c, sim, out);
-  return sim_results(c, sim, out);
+  return cons_sim_results(c, sim, out);
 }
 
 gs_status gs_consolidation_choose(const gs_consolidation* in, const gs_command* commands, uint32_t n_commands,
                                   const uint32_t* options, const double* option_prices, int32_t* chosen,
                                   uint32_t* multi_options, uint32_t* n_multi_options) {
   std::string err;
-  if (!chosen || check_input(in, &err) != GS_OK) return GS_E_INVALID;
+  if (!chosen || cons_check_input(in, &err) != GS_OK) return GS_E_INVALID;
   SimPlan sp;
   if (build_sets(in, sp, &err) != GS_OK) return GS_E_INVALID;
   if (n_commands != sp.sets.size()) return GS_E_INVALID;

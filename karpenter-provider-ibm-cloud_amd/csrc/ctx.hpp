@@ -51,6 +51,17 @@ extern "C" hipError_t gsk_ffdw_batch(const gsd::DevProblem* ds, uint32_t n, uint
                                      uint32_t lds, hipStream_t s);
 extern "C" hipError_t gsk_trunc_batch(const gsd::DevProblem* ds, uint32_t n, uint32_t max_slots, uint32_t lds_bytes,
                                       hipStream_t s);
+// ... and the consolidation simulations of a device array of problems
+extern "C" hipError_t gsk_init_ffd_sim_batch(uint32_t lds_total);
+extern "C" uint32_t gsk_ffd_sim_batch_dyn_lds_max(void);
+extern "C" uint32_t gsk_ffd_sim_batch_blocks_per_cu(uint32_t R, uint32_t lds, uint32_t nt, uint32_t general);
+extern "C" hipError_t gsk_sim_begin_batch(const gsd::DevProblem* ds, const uint32_t* blocks, uint32_t n,
+                                          uint32_t clear_overlays, hipStream_t s);
+extern "C" hipError_t gsk_ffd_sim_batch(const gsd::DevProblem* ds, const uint32_t* blocks, uint32_t n, uint32_t max_blocks,
+                                        uint32_t R, uint32_t general, uint32_t nt, uint32_t lds, uint32_t ov_epoch,
+                                        hipStream_t s);
+extern "C" hipError_t gsk_trunc_sims_batch(const gsd::DevProblem* ds, uint32_t n, uint32_t mv, uint32_t max_sims,
+                                           uint32_t max_slots, uint32_t lds_bytes, hipStream_t s);
 
 namespace gsc {
 
@@ -109,6 +120,8 @@ struct SimPlan {
 
 struct Batch;  // batch.cpp: the slots of gs_batch_*
 void batch_destroy(gs_ctx* c);
+struct ConsBatch;  // batch_consolidate.hip: the slots of gs_batch_consolidate_*
+void batch_consolidate_destroy(gs_ctx* c);
 
 }  // namespace gsc
 
@@ -117,6 +130,7 @@ struct gs_ctx {
   uint32_t cfg_flags = 0;  // gs_config.flags
   std::vector<gs_ctx*> shards;  // gs_config.n_shards > 1: one child context per shard (multi.cpp)
   gsc::Batch* batch = nullptr;  // gs_batch_*: one child context per slot, on this context's stream and events (batch.cpp)
+  gsc::ConsBatch* cons_batch = nullptr;  // gs_batch_consolidate_*: likewise (batch_consolidate.hip)
   std::vector<ncclComm_t> comms;  // GS_CFG_RCCL: one communicator rank per shard (ncclCommInitAll)
   std::string err;
   hipStream_t stream = nullptr;
@@ -156,6 +170,9 @@ struct gs_ctx {
   std::vector<double> cmd_prices;
   std::vector<uint32_t> multi_opts;
   bool cons_ready = false;
+  // the decided table's policy outcome and counter sums (cons_fill_result)
+  int32_t cons_chosen = -1;
+  uint64_t cons_checks = 0, cons_node_evals = 0, cons_node_prefix = 0, cons_pops = 0;
   // pinned per-simulation result staging (allocated with the plan)
   gsd::SimCtrl* h_ctrl = nullptr;
   std::vector<gsd::Ctrl> h_blk;  // the simulation workgroups' counter sums
@@ -283,6 +300,30 @@ uint32_t trunc_lds_bytes(uint32_t N);
 // (records: gather the Solve's first-pass queue records after the upload;
 // false for a batch slot, whose batch gathers every slot's in one launch)
 void upload_problem(gs_ctx* c, const SimPlan* sims, bool records = true);
+
+// consolidate.cpp: gs_consolidate in the steps a batch drives per slot
+// (batch_consolidate.hip): check, take the input and encode, plan, upload,
+// launch, fetch and decide.
+// threads per simulation workgroup for n simulations on a device of `cus`
+// CUs: many simulations take the narrow shape (throughput), few the wide one
+// (each simulation's latency) -- ffd_block.hpp FB_SIM / FB_SIM_NARROW
+inline uint32_t cons_sim_threads(size_t n_sims, int cus) { return n_sims >= 4 * (size_t)std::max(cus, 1) ? 128u : 256u; }
+// what a batch gives a slot's plan instead of the whole device
+struct SimBudget {
+  uint32_t nt;          // the batch's shape
+  uint64_t group_sims;  // simulations of the slot's group (the slots launched together)
+};
+gs_status cons_check_input(const gs_consolidation* in, std::string* err);
+gs_status cons_take_input(gs_ctx* c, const gs_consolidation* in);
+gs_status cons_plan_sets(gs_ctx* c, std::string* err);
+gs_status cons_plan_grid(gs_ctx* c, const SimBudget* budget, std::string* err);
+gs_status cons_upload(gs_ctx* c);
+gs_status cons_launch(gs_ctx* c);
+gs_status cons_fetch_decide(gs_ctx* c, gs_consolidation_result* out);
+void cons_fill_result(const gs_ctx* c, gs_consolidation_result* out);
+gs_status cons_sim_results(gs_ctx* c, uint32_t sim, gs_result* out);
+void reset_sim_counts(gs_ctx* c);
+void next_overlay_epoch(gs_ctx* c);
 
 }  // namespace gsc
 

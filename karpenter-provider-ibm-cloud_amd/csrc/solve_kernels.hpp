@@ -349,3 +349,45 @@ extern "C" __global__ __launch_bounds__(BLOCK) void GS_KNAME(trunc_kernel)(GS_KP
   for (uint32_t i = tid; i < take; i += BLOCK) d.c_its[(size_t)o * 60 + i] = d.rank_to_it[(uint32_t)keys[i]];
   if (tid == 0) d.c_nits[o] = take;
 }
+
+// Simulations with minValues: <U> Results.TruncateInstanceTypes drops every
+// NodeClaim flagged by trunc_kernel (all_slots); their pods become pod errors,
+// which count against the simulation when not pending
+// (AllNonPendingPodsScheduled).  One thread per simulation: the surviving
+// count, the failed pods, and the single survivor's header and top 60 in the
+// per-simulation output slot.
+extern "C" __global__ __launch_bounds__(BLOCK) void GS_KNAME(sim_fix_kernel)(GS_KPROBLEM_ARG) {
+  GS_KPROBLEM
+  const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
+  if (s >= d.n_sims) return;
+  SimCtrl& c = d.sim_ctrl[s];
+  if (c.status) return;
+  const uint32_t off = d.sim_pod_off[s], nc = c.n_claims;
+  uint32_t surv = 0, sj = NONE;
+  bool drop = false;
+  for (uint32_t j = 0; j < nc; j++) {
+    if (d.slot_drop[off + j]) {
+      drop = true;
+    } else {
+      if (!surv) sj = j;
+      surv++;
+    }
+  }
+  if (drop) {
+    uint32_t extra = 0;
+    for (uint32_t i = 0; i < c.n_log; i++) {
+      const LogRec l = d.log[off + i];
+      if (!(l.target & 0x80000000u) && d.slot_drop[off + l.target] && l.pod >= d.n_pending) extra++;
+    }
+    c.failed += extra;
+  }
+  c.n_claims = surv;
+  if (surv == 1) {
+    const uint32_t* src = (const uint32_t*)(d.c_rec + off + sj);
+    uint32_t* dst = (uint32_t*)(d.sim_hdr + s);
+    for (uint32_t q = 0; q < sizeof(ClaimRec) / 4; q++) dst[q] = src[q];
+    const uint32_t nt = d.slot_nits[off + sj];
+    for (uint32_t i = 0; i < nt; i++) d.c_its[(size_t)s * 60 + i] = d.slot_its[(size_t)(off + sj) * 60 + i];
+    d.c_nits[s] = nt;
+  }
+}

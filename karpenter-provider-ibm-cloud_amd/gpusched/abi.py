@@ -166,11 +166,11 @@ class GsConfig(C.Structure):
                 ("shard_devices", C.POINTER(C.c_int32))]
 
 
-GS_BATCH_MAX = 4096     # problems of one gs_batch_prepare
+GS_BATCH_MAX = 4096     # problems of one gs_batch_prepare, inputs of one gs_batch_consolidate_prepare
 
 
 class GsBatchStats(C.Structure):
-    """gs_batch_stats (gs_batch_last_run; size checked against gs_batch_stats_size)"""
+    """gs_batch_stats (gs_batch_last_run, gs_batch_consolidate_last_run; size checked against gs_batch_stats_size)"""
     _fields_ = [("n_problems", _U32), ("n_accepted", _U32), ("n_batched", _U32), ("n_fallback", _U32),
                 ("n_groups", _U32), ("n_launches", _U32), ("prepare_ms", C.c_double), ("run_ms", C.c_double),
                 ("device_ms", C.c_double)]

@@ -19,7 +19,9 @@ EXPORTS = ["gs_create", "gs_destroy", "gs_prepare", "gs_run", "gs_fetch", "gs_so
            "gs_consolidate", "gs_consolidate_rerun", "gs_consolidation_results", "gs_consolidation_choose", "gs_feasibility_shard",
            "gs_feasibility_shard_device", "gs_rank_instance_types", "gs_create_filter", "gs_build_catalog", "gs_build_id",
            "gs_batch_prepare", "gs_batch_run", "gs_batch_fetch", "gs_batch_error", "gs_batch_last_run",
-           "gs_batch_stats_size"]
+           "gs_batch_stats_size",
+           "gs_batch_consolidate_prepare", "gs_batch_consolidate_run", "gs_batch_consolidate_fetch",
+           "gs_batch_consolidate_results", "gs_batch_consolidate_error", "gs_batch_consolidate_last_run"]
 
 
 def source_digest():
@@ -122,6 +124,19 @@ def load():
         L.gs_batch_last_run.restype = C.c_int
         L.gs_batch_stats_size.argtypes = []
         L.gs_batch_stats_size.restype = C.c_uint32
+        L.gs_batch_consolidate_prepare.argtypes = [vp, C.POINTER(C.POINTER(abi.GsConsolidation)), C.c_uint32,
+                                                   C.POINTER(C.c_int)]
+        L.gs_batch_consolidate_prepare.restype = C.c_int
+        L.gs_batch_consolidate_run.argtypes = [vp]
+        L.gs_batch_consolidate_run.restype = C.c_int
+        L.gs_batch_consolidate_fetch.argtypes = [vp, C.c_uint32, C.POINTER(abi.GsConsolidationResult)]
+        L.gs_batch_consolidate_fetch.restype = C.c_int
+        L.gs_batch_consolidate_results.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(abi.GsResult)]
+        L.gs_batch_consolidate_results.restype = C.c_int
+        L.gs_batch_consolidate_error.argtypes = [vp, C.c_uint32, C.c_char_p, C.c_size_t]
+        L.gs_batch_consolidate_error.restype = C.c_size_t
+        L.gs_batch_consolidate_last_run.argtypes = [vp, C.POINTER(abi.GsBatchStats)]
+        L.gs_batch_consolidate_last_run.restype = C.c_int
         _lib = L
     return _lib
 
@@ -194,6 +209,7 @@ class Solver:
         self.problem = None
         self.cluster = None  # the cluster of the last consolidate (resource names of its results)
         self.batch_problems = []  # the problems of the last batch_prepare
+        self.batch_clusters = []  # the clusters of the last batch_consolidate_prepare (None: no cluster)
 
     def close(self):
         if self.ctx:
@@ -280,6 +296,60 @@ class Solver:
         """gs_batch_last_run -> dict of the gs_batch_stats fields"""
         out = abi.GsBatchStats()
         self._check(self.L.gs_batch_last_run(self.ctx, C.byref(out)))
+        return {name: getattr(out, name) for name, _ in abi.GsBatchStats._fields_}
+
+    # ---- a batch of independent consolidations (several clusters, one device)
+    def batch_consolidate_prepare(self, cins):
+        """gs_batch_consolidate_prepare: check + encode + plan + upload every
+        input -> the list of per-slot statuses (a refused slot fails neither
+        the call nor the others).  An input is a ConsolidationInput or None
+        (a NULL slot)."""
+        n = len(cins)
+        self.batch_clusters = [getattr(x, "problem", None) for x in cins]
+        null = C.POINTER(abi.GsConsolidation)()
+        ptrs = (C.POINTER(abi.GsConsolidation) * max(n, 1))(*[null if x is None else C.pointer(x.struct) for x in cins])
+        status = (C.c_int * max(n, 1))()
+        self._check(self.L.gs_batch_consolidate_prepare(self.ctx, ptrs, n, status))
+        return [int(status[i]) for i in range(n)]
+
+    def batch_consolidate_run(self):
+        """gs_batch_consolidate_run: the device part of every accepted slot"""
+        self._check(self.L.gs_batch_consolidate_run(self.ctx))
+
+    def batch_consolidate_error(self, i):
+        """gs_batch_consolidate_error: slot i's message"""
+        buf = C.create_string_buffer(1024)
+        self.L.gs_batch_consolidate_error(self.ctx, int(i), buf, 1024)
+        return buf.value.decode()
+
+    def batch_consolidate_fetch(self, i, raw=False):
+        """gs_batch_consolidate_fetch: slot i decided -> (commands, chosen,
+        multi_options, raw result), as consolidate returns them; raises with
+        the slot's own status and message when it was refused or its
+        simulations failed.  raw=True returns only the gs_consolidation_result
+        (no Python-side copy)."""
+        res = abi.GsConsolidationResult()
+        st = self.L.gs_batch_consolidate_fetch(self.ctx, int(i), C.byref(res))
+        if st != abi.GS_OK:
+            raise GpuSchedError(st, self.batch_consolidate_error(i))
+        if raw:
+            return res
+        return abi.commands_to_list(res), int(res.chosen), _multi(res), res
+
+    def batch_consolidate_results(self, i, sim):
+        """gs_batch_consolidate_results: the scheduling Results of simulation
+        `sim` of slot i -> (dict, raw gs_result), as consolidation_results
+        returns them"""
+        res = abi.GsResult()
+        st = self.L.gs_batch_consolidate_results(self.ctx, int(i), int(sim), C.byref(res))
+        if st != abi.GS_OK:
+            raise GpuSchedError(st, self.batch_consolidate_error(i))
+        return abi.result_to_dict(res, self.batch_clusters[i]), res
+
+    def batch_consolidate_stats(self):
+        """gs_batch_consolidate_last_run -> dict of the gs_batch_stats fields"""
+        out = abi.GsBatchStats()
+        self._check(self.L.gs_batch_consolidate_last_run(self.ctx, C.byref(out)))
         return {name: getattr(out, name) for name, _ in abi.GsBatchStats._fields_}
 
     def consolidate(self, cin):
