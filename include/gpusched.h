@@ -595,6 +595,48 @@ gs_status gs_batch_consolidate_run(gs_ctx* ctx);
  * i's status when it was refused.  A slot whose simulation fails fails only
  * its own fetch.  Valid until the next batch prepare or run, or gs_destroy. */
 gs_status gs_batch_consolidate_fetch(gs_ctx* ctx, uint32_t i, gs_consolidation_result* out);
+/* Every slot's outcome in one device pass: out[i] and status[i] for each of the
+ * batch's n slots (n as given to the prepare).  status[i] is what
+ * gs_batch_consolidate_fetch(ctx, i, ...) would return: the slot's prepare
+ * status when it was refused, GS_OK, or the slot's own failure, which leaves the
+ * other slots alone (message: gs_batch_consolidate_error).  For a slot with
+ * GS_OK, out[i] equals field by field what the per-slot fetch yields on the
+ * same run (commands, options, bit-equal option_prices, chosen, multi_options,
+ * pods_simulated and the four counters) and points into slot i's own storage
+ * with the same lifetime; out[i] is zeroed otherwise.  Only the t_*_ms fields
+ * differ: t_fetch_ms is the whole call's wall clock, the same value in every
+ * slot.  Afterwards every slot counts as fetched (a following per-slot fetch
+ * returns the cached table); slots fetched one by one since the run keep their
+ * tables.
+ * Cost: the slots the batched launches covered are gathered by two launches
+ * per group, one 64-byte clear, and one transfer and one synchronisation:
+ * fixed-size records (32 B per slot, 64 B per evaluated simulation) followed by
+ * the option lists (8 B per option) of the simulations that ended with exactly
+ * one NodeClaim and no failed pod.  The transfer carries as many options as the
+ * batch's previous fetch_all found; when the run left more, as in the first
+ * call after a prepare, a second transfer and synchronisation bring the rest.
+ * The number of device operations depends on the groups, not on the slots or
+ * simulations.  A slot without simulations needs no device
+ * operation; a slot the run solved alone (n_fallback) is fetched as
+ * gs_batch_consolidate_fetch does.
+ * GS_E_INVALID: NULL ctx, NULL out or status with n > 0, no prepared batch, or
+ * the batch has not run. */
+typedef struct gs_batch_fetch_stats {
+  uint32_t n_slots;     /* of the batch */
+  uint32_t n_decided;   /* accepted slots decided from the gathered records */
+  uint32_t n_per_slot;  /* accepted slots that took the per-slot path (no simulations, fallback, or
+                           already fetched since the run) */
+  uint32_t n_launches;  /* kernel launches and clears of the gather */
+  uint32_t n_copies;    /* device-to-host transfers issued (the per-slot path's included) */
+  uint64_t bytes;       /* bytes they transferred */
+  double device_ms;     /* first to last gather kernel (HIP events) */
+  double wall_ms;       /* wall clock of the call: every slot's t_fetch_ms */
+} gs_batch_fetch_stats;
+gs_status gs_batch_consolidate_fetch_all(gs_ctx* ctx, gs_consolidation_result* out /*[n]*/, gs_status* status /*[n]*/);
+/* counters and times of the last gs_batch_consolidate_fetch_all (zero before one) */
+gs_status gs_batch_consolidate_last_fetch(const gs_ctx* ctx, gs_batch_fetch_stats* out);
+/* sizeof that struct, for a binding's layout check */
+uint32_t gs_batch_fetch_stats_size(void);
 /* gs_consolidation_results for slot i: simulation `sim` runs again alone on the
  * slot's resident upload.  A following fetch and a following run return the
  * same commands.  GS_E_INVALID: the batch has not run, sim >= n_commands, or

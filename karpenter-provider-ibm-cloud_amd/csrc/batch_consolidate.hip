@@ -29,6 +29,11 @@
 //            argument, so a run copies nothing; gs_batch_consolidate_results
 //            draws the next prefix for its rerun, and when the prefix wraps
 //            every group's overlay cells are cleared (one launch per group).
+//  fetch_all every slot decided after one device pass: two launches per group
+//            (batch_kernels.hip: settle, options) pack what the decisions read
+//            into one staging buffer, which comes back in one transfer (two
+//            the first time after a prepare); cons_decide_records then decides each slot from its
+//            records, the code the per-slot fetch ends in too.
 #include <atomic>
 #include <thread>
 #include <tuple>
@@ -60,13 +65,30 @@ struct ConsBatch {
   };
   std::vector<Group> groups;
   std::vector<uint32_t> order;  // device array position -> slot
-  // the device image: order.size() DevProblem, then order.size() workgroup counts
+  // the device image: order.size() DevProblem, then order.size() workgroup
+  // counts, then each slot's first record in fetch_all's simulation table
   void* dev = nullptr;
   size_t dev_cap = 0;
   const gsd::DevProblem* problems() const { return (const gsd::DevProblem*)dev; }
   const uint32_t* blocks() const { return (const uint32_t*)((const char*)dev + order.size() * sizeof(gsd::DevProblem)); }
+  const uint32_t* sim_base() const { return blocks() + order.size(); }
   gs_batch_stats stats{};
+  // gs_batch_consolidate_fetch_all: the staging buffer (device) and its pinned
+  // mirror; both only grow.  Layout: a 64-B head whose first word is the option
+  // cursor, SlotOut[order.size()], SimOut[n_sims], then the option region
+  // (60 per simulation on the device; the mirror holds what a call transfers).
+  std::vector<uint32_t> h_sim_base;  // device array position -> first record
+  uint64_t n_sims = 0;               // simulations of the grouped slots
+  uint32_t opt_hint = 0;             // options the last fetch_all of this batch found: the next one's first transfer carries as many
+  void* g_dev = nullptr;
+  size_t g_dev_cap = 0;
+  void* g_host = nullptr;
+  size_t g_host_cap = 0;
+  gs_batch_fetch_stats fstats{};
 };
+constexpr size_t kGatherHead = 64;
+// more simulations than the 32-bit option offsets address: no gathered path
+constexpr uint64_t kGatherMaxSims = 1ull << 26;
 
 namespace {
 
@@ -109,6 +131,9 @@ void build_groups(gs_ctx* c, ConsBatch& b) {
   }
   b.groups.clear();
   b.order.clear();
+  b.h_sim_base.clear();
+  b.n_sims = 0;
+  b.opt_hint = 0;
   std::vector<gsd::DevProblem> problems;
   std::vector<uint32_t> blocks;
   for (auto& kv : by) {
@@ -131,10 +156,12 @@ void build_groups(gs_ctx* c, ConsBatch& b) {
       b.order.push_back(i);
       problems.push_back(d);
       blocks.push_back(sp.blocks);
+      b.h_sim_base.push_back((uint32_t)b.n_sims);
+      b.n_sims += d.n_sims;
     }
     b.groups.push_back(g);
   }
-  const size_t n = b.order.size(), bytes = n * (sizeof(gsd::DevProblem) + sizeof(uint32_t));
+  const size_t n = b.order.size(), bytes = n * (sizeof(gsd::DevProblem) + 2 * sizeof(uint32_t));
   if (!n) return;
   if (bytes > b.dev_cap) {
     if (b.dev) HIPCHK(hipFree(b.dev));
@@ -147,6 +174,8 @@ void build_groups(gs_ctx* c, ConsBatch& b) {
   std::vector<char> image(bytes);
   std::memcpy(image.data(), problems.data(), n * sizeof(gsd::DevProblem));
   std::memcpy(image.data() + n * sizeof(gsd::DevProblem), blocks.data(), n * sizeof(uint32_t));
+  // (meaningless past kGatherMaxSims simulations, where fetch_all does not gather)
+  std::memcpy(image.data() + n * (sizeof(gsd::DevProblem) + sizeof(uint32_t)), b.h_sim_base.data(), n * sizeof(uint32_t));
   HIPCHK(hipMemcpyAsync(b.dev, image.data(), bytes, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
 }
@@ -172,6 +201,93 @@ gs_status fetch_slot(gs_ctx* c, ConsSlot& s, gs_consolidation_result* out) {
   return s.fetch_status;
 }
 
+// gs_batch_consolidate_fetch_all's device pass: every grouped slot's records in
+// the pinned mirror.  A 64-B clear (the option cursor), two launches per group,
+// and one transfer of the head, the slot and the simulation records and the
+// options behind them.  How many options there are is the cursor's final
+// value, known after the synchronisation: the transfer carries as many as the
+// batch's last fetch_all found (a run on the same upload finds the same), and
+// only when there are more, as in the first call after a prepare, a second
+// transfer brings the rest.  Nothing here depends on how many slots there are.
+struct Gathered {
+  const gsd::SlotOut* slots = nullptr;  // [order.size()]
+  const gsd::SimOut* recs = nullptr;    // [n_sims], slot at h_sim_base
+  const gsd::OptPair* opts = nullptr;   // [n_opts], slot at SlotOut::opt_base
+  uint32_t n_opts = 0;
+};
+
+Gathered gather_all(gs_ctx* c, ConsBatch& b, gs_batch_fetch_stats& fs) {
+  const size_t ng = b.order.size();
+  const size_t recs_off = kGatherHead + ng * sizeof(gsd::SlotOut);
+  const size_t opts_off = recs_off + b.n_sims * sizeof(gsd::SimOut);
+  const size_t dev_bytes = opts_off + b.n_sims * gsd::SIM_OPTS_MAX * sizeof(gsd::OptPair);
+  if (dev_bytes > b.g_dev_cap) {
+    if (b.g_dev) HIPCHK(hipFree(b.g_dev));
+    b.g_dev = nullptr;
+    b.g_dev_cap = 0;
+    const size_t want = dev_bytes + dev_bytes / 4;
+    HIPCHK(hipMalloc(&b.g_dev, want));
+    b.g_dev_cap = want;
+  }
+  // the mirror grows to what a call transfers; `keep` bytes of it survive
+  auto grow_host = [&](size_t bytes, size_t keep) {
+    if (bytes <= b.g_host_cap) return;
+    void* p = nullptr;
+    const size_t want = bytes + bytes / 4;
+    HIPCHK(hipHostMalloc(&p, want, hipHostMallocDefault));
+    if (keep) std::memcpy(p, b.g_host, keep);
+    if (b.g_host) (void)hipHostFree(b.g_host);
+    b.g_host = p;
+    b.g_host_cap = want;
+  };
+  b.opt_hint = (uint32_t)std::min<uint64_t>(b.opt_hint, b.n_sims * gsd::SIM_OPTS_MAX);  // within the device region
+  const size_t first = opts_off + (size_t)b.opt_hint * sizeof(gsd::OptPair);
+  grow_host(first, 0);
+  char* dev = (char*)b.g_dev;
+  gsd::SlotOut* d_slots = (gsd::SlotOut*)(dev + kGatherHead);
+  gsd::SimOut* d_recs = (gsd::SimOut*)(dev + recs_off);
+  gsd::OptPair* d_opts = (gsd::OptPair*)(dev + opts_off);
+  HIPCHK(hipMemsetAsync(dev, 0, kGatherHead, c->stream));
+  HIPCHK(hipEventRecord(c->ev[6], c->stream));
+  for (const ConsBatch::Group& g : b.groups)
+    HIPCHK(gsk_cons_gather_batch(b.problems() + g.first, b.blocks() + g.first, b.sim_base() + g.first, g.count, g.max_sims,
+                                 d_slots + g.first, d_recs, d_opts, (uint32_t*)dev, c->stream));
+  HIPCHK(hipEventRecord(c->ev[7], c->stream));
+  HIPCHK(hipMemcpyAsync(b.g_host, dev, first, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  fs.n_launches = 1u + 2u * (uint32_t)b.groups.size();
+  fs.n_copies = 1;
+  fs.bytes = first;
+  Gathered g;
+  g.n_opts = *(const uint32_t*)b.g_host;
+  if (g.n_opts > b.n_sims * gsd::SIM_OPTS_MAX) throw HipError{"gs_batch_consolidate_fetch_all: corrupt option count"};
+  if (g.n_opts > b.opt_hint) {
+    const size_t bytes = (size_t)(g.n_opts - b.opt_hint) * sizeof(gsd::OptPair);
+    grow_host(first + bytes, first);
+    HIPCHK(hipMemcpyAsync((char*)b.g_host + first, d_opts + b.opt_hint, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    fs.n_copies++;
+    fs.bytes += bytes;
+  }
+  b.opt_hint = g.n_opts;
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, c->ev[6], c->ev[7]));
+  fs.device_ms = ms;
+  const char* host = (const char*)b.g_host;
+  g.slots = (const gsd::SlotOut*)(host + kGatherHead);
+  g.recs = (const gsd::SimOut*)(host + recs_off);
+  g.opts = (const gsd::OptPair*)(host + opts_off);
+  return g;
+}
+
+// a gathered slot's records address only the slot's own options
+bool records_valid(const Gathered& g, const gsd::SlotOut& so, const gsd::SimOut* rec, size_t n) {
+  if ((uint64_t)so.opt_base + so.n_opt > g.n_opts) return false;
+  for (size_t k = 0; k < n; k++)
+    if (rec[k].n_opt > gsd::SIM_OPTS_MAX || (uint64_t)rec[k].opt_off + rec[k].n_opt > so.n_opt) return false;
+  return true;
+}
+
 }  // namespace
 
 void batch_consolidate_destroy(gs_ctx* c) {
@@ -180,6 +296,8 @@ void batch_consolidate_destroy(gs_ctx* c) {
   for (auto& s : b->slots)
     if (s.c) free_slot(s.c);
   if (b->dev) (void)hipFree(b->dev);
+  if (b->g_dev) (void)hipFree(b->g_dev);
+  if (b->g_host) (void)hipHostFree(b->g_host);
   delete b;
   c->cons_batch = nullptr;
 }
@@ -203,6 +321,7 @@ gs_status gs_batch_consolidate_prepare(gs_ctx* c, const gs_consolidation* const*
   b.n = 0;
   b.groups.clear();
   b.order.clear();
+  b.fstats = gs_batch_fetch_stats{};
   while (b.slots.size() < n) {
     ConsSlot s;
     s.c = new gs_ctx();
@@ -383,6 +502,82 @@ gs_status gs_batch_consolidate_results(gs_ctx* c, uint32_t i, uint32_t sim, gs_r
   }
   return cons_sim_results(sc, sim, out);
 }
+
+gs_status gs_batch_consolidate_fetch_all(gs_ctx* c, gs_consolidation_result* out, gs_status* status) {
+  if (!c || !c->cons_batch || !c->cons_batch->prepared) return GS_E_INVALID;
+  ConsBatch& b = *c->cons_batch;
+  if (b.n && (!out || !status)) return fail(c, GS_E_INVALID, "gs_batch_consolidate_fetch_all: NULL out or status");
+  if (!b.ran) return fail(c, GS_E_INVALID, "gs_batch_consolidate_fetch_all: the batch has not run");
+  const auto t0 = Clock::now();
+  gs_batch_fetch_stats fs{};
+  fs.n_slots = b.n;
+  std::vector<uint32_t> pos_of(b.n, 0);
+  bool pending = false;
+  for (uint32_t p = 0; p < b.order.size(); p++) {
+    pos_of[b.order[p]] = p;
+    pending = pending || !b.slots[b.order[p]].fetched;
+  }
+  for (uint32_t i = 0; i < b.n; i++) {
+    status[i] = b.slots[i].status;
+    std::memset(&out[i], 0, sizeof(out[i]));
+  }
+  Gathered g;
+  bool gathered = false;
+  if (pending && b.n_sims <= kGatherMaxSims) {
+    try {
+      HIPCHK(hipSetDevice(c->device));
+      g = gather_all(c, b, fs);
+      gathered = true;
+    } catch (const HipError& e) {
+      return fail(c, GS_E_HIP, e.msg);
+    }
+  }
+  for (uint32_t i = 0; i < b.n; i++) {
+    ConsSlot& s = b.slots[i];
+    if (s.status != GS_OK) continue;
+    if (!s.fetched && s.grouped && gathered) {
+      const uint32_t p = pos_of[i];
+      const gsd::SlotOut& so = g.slots[p];
+      const gsd::SimOut* rec = g.recs + b.h_sim_base[p];
+      if (records_valid(g, so, rec, s.c->sims.evaluated.size()))
+        s.fetch_status = cons_decide_records(s.c, rec, g.opts + so.opt_base, so);
+      else
+        s.fetch_status = fail(s.c, GS_E_HIP, "gs_batch_consolidate_fetch_all: corrupt simulation records");
+      s.fetched = true;
+      status[i] = s.fetch_status;
+      fs.n_decided++;
+      continue;
+    }
+    // no gather: a slot without simulations (no device operation), a fallback
+    // slot, or one fetched since the run (its table is kept)
+    if (!s.fetched && !s.c->sims.evaluated.empty()) {
+      const size_t ns = s.c->sims.evaluated.size();
+      fs.n_copies += 5;
+      fs.bytes += ns * (sizeof(gsd::SimCtrl) + sizeof(gsd::ClaimRec) + 61 * sizeof(uint32_t)) +
+                  s.c->sims.blocks * sizeof(gsd::Ctrl);
+    }
+    gs_consolidation_result table;
+    status[i] = fetch_slot(c, s, &table);
+    fs.n_per_slot++;
+  }
+  fs.wall_ms = ms_since(t0);
+  for (uint32_t i = 0; i < b.n; i++) {
+    if (status[i] != GS_OK) continue;
+    gs_ctx* sc = b.slots[i].c;
+    sc->t_fetch = fs.wall_ms;
+    cons_fill_result(sc, &out[i]);
+  }
+  b.fstats = fs;
+  return GS_OK;
+}
+
+gs_status gs_batch_consolidate_last_fetch(const gs_ctx* c, gs_batch_fetch_stats* out) {
+  if (!c || !out || !c->cons_batch || !c->cons_batch->prepared) return GS_E_INVALID;
+  *out = c->cons_batch->fstats;
+  return GS_OK;
+}
+
+uint32_t gs_batch_fetch_stats_size(void) { return (uint32_t)sizeof(gs_batch_fetch_stats); }
 
 size_t gs_batch_consolidate_error(const gs_ctx* c, uint32_t i, char* buf, size_t len) {
   if (!c || !c->cons_batch || i >= c->cons_batch->n) return 0;

@@ -243,3 +243,130 @@ extern "C" hipError_t gsk_ffd_sim_batch(const DevProblem* ds, const uint32_t* bl
       return hipErrorInvalidValue;
   }
 }
+
+// ===================== every slot's outcome in one pass (gs_batch_consolidate_fetch_all)
+// Two kernels per group over the array the run used, writing into one
+// batch-wide staging buffer: SlotOut per slot, SimOut per evaluated simulation
+// (slot y's simulation k at recs[sim_base[y] + k]: the host knows every slot's
+// simulation count from its plan), and the options of the single-NodeClaim
+// simulations compacted behind one another.
+//
+// Option offsets: the settle kernel scans the slot's option counts in
+// simulation order (SimOut::opt_off, relative to the slot) and takes the slot's
+// share of the option region with one atomic add on the batch's cursor, which
+// the host clears before the first group (SlotOut::opt_base).  Slots therefore
+// lie in the region in arrival order; each slot's options are in simulation
+// order.  The cursor's final value is the number of options to transfer.
+
+// One workgroup per slot: the outcome records and the counter sums.
+extern "C" __global__ __launch_bounds__(256) void cons_settle_kernel_batch(const DevProblem* __restrict__ ds,
+                                                                           const uint32_t* __restrict__ blocks,
+                                                                           const uint32_t* __restrict__ sim_base,
+                                                                           SlotOut* __restrict__ slots,
+                                                                           SimOut* __restrict__ recs,
+                                                                           uint32_t* __restrict__ cursor) {
+  const DevProblem& d = ds[blockIdx.y];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t NS = d.n_sims;
+  SimOut* out = recs + sim_base[blockIdx.y];
+  __shared__ uint32_t s_wave[4];
+  __shared__ unsigned long long s_sum[3];
+  if (tid < 3) s_sum[tid] = 0;
+  uint32_t run = 0;  // options of the simulations before this chunk (uniform)
+  for (uint32_t k0 = 0; k0 < NS; k0 += 256) {
+    const uint32_t k = k0 + tid;
+    SimOut o{};
+    if (k < NS) {
+      const SimCtrl ct = d.sim_ctrl[k];
+      o.status = ct.status;
+      o.n_claims = ct.n_claims;
+      o.failed = ct.failed;
+      if (ct.status == 0 && ct.failed == 0 && ct.n_claims == 1) {
+        const ClaimRec& h = d.sim_hdr[k];
+        o.tmpl = h.tmpl;
+        o.ctb = h.ctb;
+        o.zflags = h.zflags;
+        o.zfull = h.zfull;
+        o.zm = h.zm;
+        o.cm = h.cm;
+        const uint32_t n = d.c_nits[k];
+        o.n_opt = n < SIM_OPTS_MAX ? n : SIM_OPTS_MAX;
+      }
+    }
+    // exclusive scan of n_opt over the chunk: within the wave, then over the 4 waves
+    uint32_t incl = o.n_opt;
+    for (uint32_t s = 1; s < 64; s <<= 1) {
+      const uint32_t up = __shfl_up(incl, s, 64);
+      if (lane >= s) incl += up;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+    for (uint32_t w = 0; w < 4; w++) {
+      before += w < wave ? s_wave[w] : 0u;
+      total += s_wave[w];
+    }
+    __syncthreads();  // s_wave is rewritten by the next chunk
+    if (k < NS) {
+      o.opt_off = run + before + incl - o.n_opt;
+      out[k] = o;
+    }
+    run += total;
+  }
+  // the simulation workgroups' counters
+  unsigned long long ne = 0, np = 0, pp = 0;
+  for (uint32_t b = tid; b < blocks[blockIdx.y]; b += 256) {
+    const Ctrl& c = d.sim_blk[b];
+    ne += c.node_evals;
+    np += c.node_prefix;
+    pp += c.pops;
+  }
+  __syncthreads();  // s_sum cleared
+  if (ne) atomicAdd(&s_sum[0], ne);
+  if (np) atomicAdd(&s_sum[1], np);
+  if (pp) atomicAdd(&s_sum[2], pp);
+  __syncthreads();
+  if (tid == 0) {
+    SlotOut so;
+    so.node_evals = s_sum[0];
+    so.node_prefix = s_sum[1];
+    so.pops = s_sum[2];
+    so.n_opt = run;
+    so.opt_base = run ? atomicAdd(cursor, run) : 0u;
+    slots[blockIdx.y] = so;
+  }
+}
+
+// One wave per evaluated simulation, one lane per option: the instance type
+// and the price rank of its cheapest available offering on the NodeClaim's grid
+// (cons_fetch_decide's inner loop).  gridDim.x is sized for the group's largest
+// slot; a wave past its own slot's simulations, or whose simulation has no
+// option list, returns (no barrier, no LDS).
+extern "C" __global__ __launch_bounds__(256) void cons_options_kernel_batch(const DevProblem* __restrict__ ds,
+                                                                            const uint32_t* __restrict__ sim_base,
+                                                                            const SlotOut* __restrict__ slots,
+                                                                            const SimOut* __restrict__ recs,
+                                                                            OptPair* __restrict__ opts) {
+  const DevProblem& d = ds[blockIdx.y];
+  const uint32_t k = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (k >= d.n_sims) return;
+  const SimOut& o = recs[sim_base[blockIdx.y] + k];
+  if (lane >= o.n_opt) return;
+  const uint32_t it = d.c_its[(size_t)k * 60 + lane];
+  OptPair p;
+  p.it = it;
+  p.minp = it < d.N ? option_min_rank(d.it_pair, d.it_prank, it, pair_grid(o.zm, o.cm, d.Z, d.C)) : NONE;
+  opts[(size_t)slots[blockIdx.y].opt_base + o.opt_off + lane] = p;
+}
+
+// n slots of one group (ds, blocks, sim_base and slots point at the group's
+// first): two launches.  max_sims: the largest slot's simulations.
+extern "C" hipError_t gsk_cons_gather_batch(const DevProblem* ds, const uint32_t* blocks, const uint32_t* sim_base,
+                                            uint32_t n, uint32_t max_sims, SlotOut* slots, SimOut* recs, OptPair* opts,
+                                            uint32_t* cursor, hipStream_t s) {
+  if (!n || n > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cons_settle_kernel_batch, dim3(1, n), dim3(256), 0, s, ds, blocks, sim_base, slots, recs, cursor);
+  hipLaunchKernelGGL(cons_options_kernel_batch, dim3(max_sims ? (max_sims + 3) / 4 : 1, n), dim3(256), 0, s, ds, sim_base,
+                     (const SlotOut*)slots, (const SimOut*)recs, opts);
+  return hipGetLastError();
+}

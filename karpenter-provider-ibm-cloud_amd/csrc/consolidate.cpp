@@ -180,14 +180,6 @@ gs_status build_sets(const gs_consolidation* in, SimPlan& sp, std::string* err) 
   return GS_OK;
 }
 
-uint64_t grid_of(uint64_t zm, uint64_t cm, uint32_t Z, uint32_t C) {
-  const uint64_t cmask = C >= 64 ? ~0ull : ((1ull << C) - 1);
-  uint64_t g = 0;
-  for (uint32_t z = 0; z < Z; z++)
-    if ((zm >> z) & 1) g |= (cm & cmask) << (z * C);
-  return g;
-}
-
 // <U> filterOutSameInstanceType: indices of the options that survive
 std::vector<uint32_t> filter_out_same_type(const CandTable& t, const std::vector<uint32_t>& cands,
                                            const uint32_t* opts, const double* prices, uint32_t n) {
@@ -439,18 +431,13 @@ gs_status cons_launch(gs_ctx* c) {
   return GS_OK;
 }
 
-// step 5: copy every evaluated simulation's outcome back and decide it
-// (computeConsolidation per simulation, then the mode's policy)
+// step 5: copy every evaluated simulation's outcome back, pack it into the
+// records the decision reads, and decide
 gs_status cons_fetch_decide(gs_ctx* c, gs_consolidation_result* out) {
   const gsh::Encoded& e = c->enc;
   const SimPlan& sp = c->sims;
-  const gs_consolidation* in = &c->cons_in;
   auto& d = c->dp;
   const size_t NS = sp.evaluated.size();
-  const gsd::SimCtrl* ctrl = c->h_ctrl;
-  const gsd::ClaimRec* hdr = c->h_hdr;
-  const uint32_t* its = c->h_its;
-  const uint32_t* nits = c->h_nits;
   auto t0 = Clock::now();
   try {
     if (NS) {
@@ -468,6 +455,55 @@ gs_status cons_fetch_decide(gs_ctx* c, gs_consolidation_result* out) {
   } catch (const HipError& ex) {
     return fail(c, GS_E_HIP, ex.msg);
   }
+  // the copies as records: what batch_kernels.hip's settle and option kernels
+  // write for a whole batch
+  gsd::SlotOut sums{};
+  if (NS)
+    for (const gsd::Ctrl& b : c->h_blk) {
+      sums.node_evals += b.node_evals;
+      sums.node_prefix += b.node_prefix;
+      sums.pops += b.pops;
+    }
+  c->h_rec.assign(NS, gsd::SimOut{});
+  c->h_pairs.clear();
+  for (size_t k = 0; k < NS; k++) {
+    const gsd::SimCtrl& ct = c->h_ctrl[k];
+    gsd::SimOut& o = c->h_rec[k];
+    o.status = ct.status;
+    o.n_claims = ct.n_claims;
+    o.failed = ct.failed;
+    if (ct.status != 0 || ct.failed != 0 || ct.n_claims != 1) continue;
+    const gsd::ClaimRec& h = c->h_hdr[k];
+    o.tmpl = h.tmpl;
+    o.ctb = h.ctb;
+    o.zflags = h.zflags;
+    o.zfull = h.zfull;
+    o.zm = h.zm;
+    o.cm = h.cm;
+    o.n_opt = std::min(c->h_nits[k], gsd::SIM_OPTS_MAX);
+    o.opt_off = (uint32_t)c->h_pairs.size();
+    const uint64_t G = gsd::pair_grid(h.zm, h.cm, e.Z, e.C);
+    for (uint32_t i = 0; i < o.n_opt; i++) {
+      const uint32_t it = c->h_its[k * 60 + i];
+      c->h_pairs.push_back({it, gsd::option_min_rank(e.it_pair.data(), e.it_prank.data(), it, G)});
+    }
+  }
+  const gs_status st = cons_decide_records(c, c->h_rec.data(), c->h_pairs.data(), sums);
+  if (st != GS_OK) return st;
+  c->t_fetch = ms_since(t0);
+  cons_fill_result(c, out);
+  return GS_OK;
+}
+
+// ... decide from records: computeConsolidation per evaluated simulation
+// (rec[k]; its options at opts[rec[k].opt_off ...]), then the mode's policy.
+// The one statement of the decision rules: the per-slot fetch above and
+// gs_batch_consolidate_fetch_all (batch_consolidate.hip) both end here.
+gs_status cons_decide_records(gs_ctx* c, const gsd::SimOut* rec, const gsd::OptPair* opts, const gsd::SlotOut& sums) {
+  const gsh::Encoded& e = c->enc;
+  const SimPlan& sp = c->sims;
+  const gs_consolidation* in = &c->cons_in;
+  const size_t NS = sp.evaluated.size();
   c->commands.assign(sp.sets.size(), gs_command{});
   c->cmd_options.clear();
   c->cmd_prices.clear();
@@ -475,38 +511,32 @@ gs_status cons_fetch_decide(gs_ctx* c, gs_consolidation_result* out) {
     c->commands[s].decision = GS_DECISION_SKIPPED;
     c->commands[s].n_candidates = (uint32_t)sp.sets[s].size();
   }
-  uint64_t checks = 0, node_evals = 0, pops = 0, node_prefix = 0;
-  if (NS)
-    for (const gsd::Ctrl& b : c->h_blk) {
-      node_evals += b.node_evals;
-      node_prefix += b.node_prefix;
-      pops += b.pops;
-    }
+  uint64_t checks = 0;
   for (size_t k = 0; k < NS; k++) {
     const uint32_t s = sp.evaluated[k];
-    const gsd::SimCtrl& ct = ctrl[k];
-    if (ct.status != 0) reset_sim_counts(c);
-    if (ct.status == gsd::ST_POD_COUNT)
+    const gsd::SimOut& h = rec[k];
+    if (h.status != 0) reset_sim_counts(c);
+    if (h.status == gsd::ST_POD_COUNT)
       return fail(c, GS_E_CAPACITY, "a simulated NodeClaim would hold more than 65535 pods (16-bit pod count)");
-    if (ct.status != 0) return fail(c, GS_E_HIP, "simulation kernel reported an internal error");
+    if (h.status != 0) return fail(c, GS_E_HIP, "simulation kernel reported an internal error");
     const uint32_t q0 = sp.pod_off[k], P = sp.pod_off[k + 1] - q0;
     checks += (uint64_t)P * (e.NN - sp.sets[s].size() + e.checks_per_pod);
     gs_command& cmd = c->commands[s];
     cmd.decision = GS_DECISION_NOOP;
-    cmd.n_new_claims = ct.n_claims;
+    cmd.n_new_claims = h.n_claims;
     // !AllNonPendingPodsScheduled: unplaced non-pending pods, and non-pending
     // pods placed on uninitialized nodes (SimulateScheduling; counted on device)
-    const uint32_t failed = ct.failed;
+    const uint32_t failed = h.failed;
     cmd.n_failed_pods = failed;
     if (failed) {
       cmd.reason = GS_NOOP_UNSCHEDULABLE;
       continue;
     }
-    if (ct.n_claims == 0) {
+    if (h.n_claims == 0) {
       cmd.decision = GS_DECISION_DELETE;
       continue;
     }
-    if (ct.n_claims > 1) {
+    if (h.n_claims > 1) {
       cmd.reason = GS_NOOP_MULTIPLE_CLAIMS;
       continue;
     }
@@ -524,7 +554,6 @@ gs_status cons_fetch_decide(gs_ctx* c, gs_consolidation_result* out) {
     }
     cmd.candidate_price = cp;
     // the NodeClaim's capacity-type requirement: template AND every added pod
-    const gsd::ClaimRec& h = hdr[k];
     bool has_spot = (h.ctb & gsd::CT_SPOT) != 0;
     bool has_od = (h.ctb & gsd::CT_OD) != 0;
     if (e.dom_ct && !(h.zflags & gsd::ZF_COMP)) {
@@ -544,21 +573,16 @@ gs_status cons_fetch_decide(gs_ctx* c, gs_consolidation_result* out) {
       continue;
     }
     // RemoveInstanceTypeOptionsByPriceAndMinValues over the OrderByPrice list
-    // (the price filter, then SatisfiesMinValues on what is left)
-    const uint64_t G = grid_of(h.zm, h.cm, e.Z, e.C);
+    // (the price filter, then SatisfiesMinValues on what is left); an option's
+    // price is its cheapest available offering's on the claim's grid (minp)
+    if (h.tmpl >= e.tmpl.size() || h.n_opt > gsd::SIM_OPTS_MAX)
+      return fail(c, GS_E_HIP, "simulation kernel reported an internal error");
     const uint32_t ob = (uint32_t)c->cmd_options.size();
-    for (uint32_t i = 0; i < nits[k]; i++) {
-      const uint32_t it = its[k * 60 + i];
-      uint32_t minp = gsd::NONE;
-      uint64_t m = e.it_pair[it] & G;
-      while (m) {
-        const uint32_t g = (uint32_t)__builtin_ctzll(m);
-        m &= m - 1;
-        minp = std::min(minp, e.it_prank[(size_t)it * 64 + g]);
-      }
-      const double pr = minp == gsd::NONE ? __DBL_MAX__ : e.prices[minp];
+    for (uint32_t i = 0; i < h.n_opt; i++) {
+      const gsd::OptPair& o = opts[h.opt_off + i];
+      const double pr = o.minp == gsd::NONE ? __DBL_MAX__ : e.prices[o.minp];
       if (pr < cp) {
-        c->cmd_options.push_back(it);
+        c->cmd_options.push_back(o.it);
         c->cmd_prices.push_back(pr);
       }
     }
@@ -584,13 +608,11 @@ gs_status cons_fetch_decide(gs_ctx* c, gs_consolidation_result* out) {
   if (NS == sp.sets.size())
     chosen = choose(c->cand_table, in->mode, sp.sets, sp.multi_max, c->commands.data(), c->cmd_options.data(),
                     c->cmd_prices.data(), &c->multi_opts);
-  c->t_fetch = ms_since(t0);
   c->cons_chosen = chosen;
   c->cons_checks = checks;
-  c->cons_node_evals = node_evals;
-  c->cons_node_prefix = node_prefix;
-  c->cons_pops = pops;
-  cons_fill_result(c, out);
+  c->cons_node_evals = sums.node_evals;
+  c->cons_node_prefix = sums.node_prefix;
+  c->cons_pops = sums.pops;
   return GS_OK;
 }
 

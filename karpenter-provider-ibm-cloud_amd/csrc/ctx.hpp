@@ -62,6 +62,9 @@ extern "C" hipError_t gsk_ffd_sim_batch(const gsd::DevProblem* ds, const uint32_
                                         hipStream_t s);
 extern "C" hipError_t gsk_trunc_sims_batch(const gsd::DevProblem* ds, uint32_t n, uint32_t mv, uint32_t max_sims,
                                            uint32_t max_slots, uint32_t lds_bytes, hipStream_t s);
+extern "C" hipError_t gsk_cons_gather_batch(const gsd::DevProblem* ds, const uint32_t* blocks, const uint32_t* sim_base,
+                                            uint32_t n, uint32_t max_sims, gsd::SlotOut* slots, gsd::SimOut* recs,
+                                            gsd::OptPair* opts, uint32_t* cursor, hipStream_t s);
 
 namespace gsc {
 
@@ -179,6 +182,9 @@ struct gs_ctx {
   gsd::ClaimRec* h_hdr = nullptr;
   uint32_t* h_its = nullptr;
   uint32_t* h_nits = nullptr;
+  // ... and the same as the records the decision reads (cons_decide_records)
+  std::vector<gsd::SimOut> h_rec;
+  std::vector<gsd::OptPair> h_pairs;
   double t_sim = 0;
   // gs_consolidation_results: the re-run simulation's per-NodeClaim top 60
   // (device; one slot per pod of the largest simulation)
@@ -320,6 +326,9 @@ gs_status cons_plan_grid(gs_ctx* c, const SimBudget* budget, std::string* err);
 gs_status cons_upload(gs_ctx* c);
 gs_status cons_launch(gs_ctx* c);
 gs_status cons_fetch_decide(gs_ctx* c, gs_consolidation_result* out);
+// the decision alone, from packed records: rec[k] per evaluated simulation, its
+// options at opts[rec[k].opt_off ...], the slot's counter sums
+gs_status cons_decide_records(gs_ctx* c, const gsd::SimOut* rec, const gsd::OptPair* opts, const gsd::SlotOut& sums);
 void cons_fill_result(const gs_ctx* c, gs_consolidation_result* out);
 gs_status cons_sim_results(gs_ctx* c, uint32_t sim, gs_result* out);
 void reset_sim_counts(gs_ctx* c);

@@ -239,6 +239,57 @@ struct SimCtrl {
   uint32_t status, n_claims, n_log, failed;
 };
 
+// What computeConsolidation reads of one evaluated simulation, packed
+// (consolidate.cpp cons_decide_records).  The per-slot fetch builds these on
+// the host from what it copies back; gs_batch_consolidate_fetch_all has the
+// device write them for every slot of a batch (batch_kernels.hip).  The header
+// fields and the option list are set only for a simulation that ended with
+// exactly one NodeClaim and no failed pod (n_opt 0 otherwise): the only case
+// that is priced.
+struct SimOut {
+  uint32_t status, n_claims, failed;
+  uint32_t n_opt;        // OrderByPrice + Truncate(60) options of the single NodeClaim
+  uint32_t tmpl, ctb, zflags;
+  uint32_t opt_off;      // first option, relative to the slot's SlotOut::opt_base
+  uint64_t zfull, zm, cm;
+  uint64_t pad;
+};
+static_assert(sizeof(SimOut) == 64, "SimOut layout");
+// one option: the instance type and the price rank of its cheapest available
+// offering on the NodeClaim's (zone, capacity type) grid, NONE without one
+struct OptPair {
+  uint32_t it, minp;
+};
+// per slot: the simulation workgroups' counter sums and the slot's options
+struct SlotOut {
+  uint64_t node_evals, node_prefix, pops;
+  uint32_t opt_base, n_opt;
+};
+static_assert(sizeof(SlotOut) == 32, "SlotOut layout");
+constexpr uint32_t SIM_OPTS_MAX = 60;  // Truncate(60): the options of one simulation
+
+// the offering grid (bit z * C + c) of a zone mask and a capacity-type mask
+__host__ __device__ inline uint64_t pair_grid(uint64_t zm, uint64_t cm, uint32_t Z, uint32_t C) {
+  const uint64_t cmask = C >= 64 ? ~0ull : ((1ull << C) - 1);
+  uint64_t g = 0;
+  for (uint32_t z = 0; z < Z && z * C < 64; z++)
+    if ((zm >> z) & 1) g |= (cm & cmask) << (z * C);
+  return g;
+}
+// an option's price rank on grid G: the minimum over the type's available pairs
+__host__ __device__ inline uint32_t option_min_rank(const uint64_t* it_pair, const uint32_t* it_prank, uint32_t it,
+                                                    uint64_t G) {
+  uint32_t minp = NONE;
+  uint64_t m = it_pair[it] & G;
+  while (m) {
+    const uint32_t g = (uint32_t)__builtin_ctzll(m);
+    m &= m - 1;
+    const uint32_t r = it_prank[(size_t)it * 64 + g];
+    minp = r < minp ? r : minp;
+  }
+  return minp;
+}
+
 struct DevProblem {
   // sizes
   uint32_t N, W, R, Z, C, T, F, V, P, K, NT;  // K = IT keys, NT = taint vocab

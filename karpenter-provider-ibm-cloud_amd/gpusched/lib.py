@@ -21,7 +21,8 @@ EXPORTS = ["gs_create", "gs_destroy", "gs_prepare", "gs_run", "gs_fetch", "gs_so
            "gs_batch_prepare", "gs_batch_run", "gs_batch_fetch", "gs_batch_error", "gs_batch_last_run",
            "gs_batch_stats_size",
            "gs_batch_consolidate_prepare", "gs_batch_consolidate_run", "gs_batch_consolidate_fetch",
-           "gs_batch_consolidate_results", "gs_batch_consolidate_error", "gs_batch_consolidate_last_run"]
+           "gs_batch_consolidate_results", "gs_batch_consolidate_error", "gs_batch_consolidate_last_run",
+           "gs_batch_consolidate_fetch_all", "gs_batch_consolidate_last_fetch", "gs_batch_fetch_stats_size"]
 
 
 def source_digest():
@@ -137,6 +138,12 @@ def load():
         L.gs_batch_consolidate_error.restype = C.c_size_t
         L.gs_batch_consolidate_last_run.argtypes = [vp, C.POINTER(abi.GsBatchStats)]
         L.gs_batch_consolidate_last_run.restype = C.c_int
+        L.gs_batch_consolidate_fetch_all.argtypes = [vp, C.POINTER(abi.GsConsolidationResult), C.POINTER(C.c_int)]
+        L.gs_batch_consolidate_fetch_all.restype = C.c_int
+        L.gs_batch_consolidate_last_fetch.argtypes = [vp, C.POINTER(abi.GsBatchFetchStats)]
+        L.gs_batch_consolidate_last_fetch.restype = C.c_int
+        L.gs_batch_fetch_stats_size.argtypes = []
+        L.gs_batch_fetch_stats_size.restype = C.c_uint32
         _lib = L
     return _lib
 
@@ -335,6 +342,30 @@ class Solver:
         if raw:
             return res
         return abi.commands_to_list(res), int(res.chosen), _multi(res), res
+
+    def batch_consolidate_fetch_all(self, raw=False):
+        """gs_batch_consolidate_fetch_all: every slot decided in one device
+        pass -> (tables, statuses).  tables[i] is what batch_consolidate_fetch(i)
+        returns, (commands, chosen, multi_options, raw result), or None where
+        statuses[i] is not GS_OK (batch_consolidate_error(i) has the message).
+        raw=True returns the gs_consolidation_result array instead of the
+        tables (no Python-side copy)."""
+        n = len(self.batch_clusters)
+        res = (abi.GsConsolidationResult * max(n, 1))()
+        status = (C.c_int * max(n, 1))()
+        self._check(self.L.gs_batch_consolidate_fetch_all(self.ctx, res, status))
+        statuses = [int(status[i]) for i in range(n)]
+        if raw:
+            return res, statuses
+        tables = [(abi.commands_to_list(res[i]), int(res[i].chosen), _multi(res[i]), res[i])
+                  if statuses[i] == abi.GS_OK else None for i in range(n)]
+        return tables, statuses
+
+    def batch_consolidate_fetch_stats(self):
+        """gs_batch_consolidate_last_fetch -> dict of the gs_batch_fetch_stats fields"""
+        out = abi.GsBatchFetchStats()
+        self._check(self.L.gs_batch_consolidate_last_fetch(self.ctx, C.byref(out)))
+        return {name: getattr(out, name) for name, _ in abi.GsBatchFetchStats._fields_}
 
     def batch_consolidate_results(self, i, sim):
         """gs_batch_consolidate_results: the scheduling Results of simulation
