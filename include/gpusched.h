@@ -751,6 +751,62 @@ typedef struct gs_claim_filter_result {
 gs_status gs_create_filter(gs_ctx* ctx, const gs_problem* catalog, const gs_claim_query* queries,
                            uint32_t n_queries, gs_claim_filter_result* out);
 
+/* ---- the same re-filter against a catalog kept on the device -------------
+ * Between two catalog lists only the UnavailableOfferings overlay changes, so
+ * the catalog is reduced and uploaded once (prepare), every Create re-filters
+ * against it (run: only the claims are reduced and sent), and a failed launch
+ * patches the availability in place (set_available).  The resident catalog is
+ * separate from gs_create_filter on the same context: neither uses nor
+ * disturbs the other. */
+#define GS_CF_BITSETS 1u /* run flag: return the `compatible` and `requirements` bitsets as well */
+/* counters and times of the last prepare or run */
+typedef struct gs_create_filter_stats {
+  double encode_ms;   /* host: reducing the requirement lists and building the upload image */
+  double upload_ms;   /* host clock: prepare: allocation + transfer, waited for; run: enqueueing the
+                         transfer and the launch */
+  double kernel_ms;   /* run: claim_select_kernel (HIP events) */
+  double fetch_ms;    /* run, host clock: the copy back, waiting for the device, unpacking the records */
+  uint64_t h2d_bytes; /* bytes sent to the device (a run sends nothing of the catalog) */
+  uint64_t d2h_bytes; /* bytes copied back: 16 per claim, plus 16 * words per claim under GS_CF_BITSETS */
+  uint32_t n_launches;
+  uint32_t n_queries;
+  uint32_t n_instance_types;
+  uint32_t n_staged_lds; /* run: claims whose reduced list the kernel staged in LDS (at most 32 keys and
+                            1,024 values in all; the others are read from HBM) */
+} gs_create_filter_stats;
+/* Reduce and upload the catalog (the fields gs_create_filter reads, with the
+ * same checks and messages).  Allocatable() is kept over every resource a
+ * capacity list names.  The encoding happens on the host before the device is
+ * touched: a prepare that fails leaves the previous resident catalog
+ * answering.  A catalog without instance types is valid.  A second prepare
+ * replaces the first. */
+gs_status gs_create_filter_prepare(gs_ctx* ctx, const gs_problem* catalog);
+/* Re-filter n_queries NodeClaims against the resident catalog.  `pool` holds
+ * the claims' data only: its strings, value_ids, reqs and quantities are read
+ * and the queries' ranges point into it.  Its string ids are unrelated to the
+ * catalog's: keys (after label normalisation), values and resource names match
+ * by text.  Keys and values the catalog has never seen get ids for this call
+ * only; a requested resource no capacity list names reads as allocatable 0.
+ * flags: 0 or GS_CF_BITSETS.  Without GS_CF_BITSETS out->compatible and
+ * out->requirements are NULL and only n_compatible, selected and capacity_type
+ * come back (16 B per claim cross the bus); out->words is set either way.
+ * GS_E_INVALID: no resident catalog, more than 65,535 claims, a null pool
+ * array with a non-zero count, or a bad claim exactly as gs_create_filter
+ * refuses it; the resident catalog stays usable after any of them.  Results
+ * are owned by the ctx until the next run, prepare or gs_destroy. */
+gs_status gs_create_filter_run(gs_ctx* ctx, const gs_problem* pool, const gs_claim_query* queries,
+                               uint32_t n_queries, uint32_t flags, gs_claim_filter_result* out);
+/* The UnavailableOfferings overlay on the resident catalog: offering[i] is an
+ * index into the prepared catalog's `offerings` array and takes
+ * available[i] != 0, in every instance type whose offering range holds it.
+ * Applied in order (a repeated index takes its last value), before the next
+ * run, in one transfer whatever n is.  An index out of range: GS_E_INVALID and
+ * nothing changes.  n = 0 is valid. */
+gs_status gs_create_filter_set_available(gs_ctx* ctx, const uint32_t* offering, const uint8_t* available, uint32_t n);
+gs_status gs_create_filter_last_run(const gs_ctx* ctx, gs_create_filter_stats* out);
+/* sizeof the stats struct, for a binding's layout check */
+uint32_t gs_create_filter_stats_size(void);
+
 /* ------------------------------------------------------ catalog ingest
  * IBMInstanceTypeProvider.List over the VPC wire data (reference
  * pkg/providers/common/instancetype/instancetype.go:221-246,433-537,659-858;

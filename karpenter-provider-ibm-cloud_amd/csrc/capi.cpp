@@ -653,7 +653,7 @@ void gs_destroy(gs_ctx* c) {
   c->free_all();
   if (c->arena) (void)hipFree(c->arena);
   if (c->stage) (void)hipHostFree(c->stage);
-  if (c->cf_dev) (void)hipFree(c->cf_dev);
+  create_filter_destroy(c);
   for (auto& e : c->ev)
     if (e) (void)hipEventDestroy(e);
   if (c->stream) (void)hipStreamDestroy(c->stream);

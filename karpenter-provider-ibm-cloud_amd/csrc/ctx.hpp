@@ -125,8 +125,12 @@ struct Batch;  // batch.cpp: the slots of gs_batch_*
 void batch_destroy(gs_ctx* c);
 struct ConsBatch;  // batch_consolidate.hip: the slots of gs_batch_consolidate_*
 void batch_consolidate_destroy(gs_ctx* c);
+void create_filter_destroy(gs_ctx* c);  // filter.hip: the re-filter's arena and its resident catalog
 
 }  // namespace gsc
+namespace gsf {
+struct Resident;  // filter.hip: gs_create_filter_prepare's catalog and the runs' buffers
+}
 
 struct gs_ctx {
   int device = 0;
@@ -199,6 +203,7 @@ struct gs_ctx {
   std::vector<uint32_t> cf_n, cf_ct;
   std::vector<int32_t> cf_sel;
   double t_filter = 0;
+  gsf::Resident* cf_res = nullptr;  // gs_create_filter_prepare / _run: separate from the arena above
   // gs_build_catalog result storage
   std::vector<std::string> cat_strs, cat_reasons;
   std::vector<const char*> cat_ptrs, cat_reason_ptrs;

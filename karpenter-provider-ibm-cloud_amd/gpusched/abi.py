@@ -296,18 +296,29 @@ class GsClaimFilterResult(C.Structure):
     ]
 
 
+GS_CF_BITSETS = 1       # gs_create_filter_run flag: return the two bitsets as well
+
+
+class GsCreateFilterStats(C.Structure):
+    """gs_create_filter_stats (gs_create_filter_last_run; size checked against gs_create_filter_stats_size)"""
+    _fields_ = [("encode_ms", C.c_double), ("upload_ms", C.c_double), ("kernel_ms", C.c_double),
+                ("fetch_ms", C.c_double), ("h2d_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64),
+                ("n_launches", _U32), ("n_queries", _U32), ("n_instance_types", _U32), ("n_staged_lds", _U32)]
+
+
 def _bits(ptr, q, words, n):
     return [64 * w + i for w in range(words) for i in range(64)
             if (ptr[q * words + w] >> i) & 1 and 64 * w + i < n]
 
 
-def claim_filter_to_list(res: GsClaimFilterResult, n_types: int) -> list:
+def claim_filter_to_list(res: GsClaimFilterResult, n_types: int, bitsets: bool = True) -> list:
     """per query: {compatible: [catalog indices], requirements: [...],
-    selected, capacity_type} (List order)"""
+    selected, capacity_type} (List order); bitsets=False (a run without
+    GS_CF_BITSETS): compatible and requirements are None"""
     out = []
     for q in range(res.n_queries):
-        out.append(dict(compatible=_bits(res.compatible, q, res.words, n_types),
-                        requirements=_bits(res.requirements, q, res.words, n_types),
+        out.append(dict(compatible=_bits(res.compatible, q, res.words, n_types) if bitsets else None,
+                        requirements=_bits(res.requirements, q, res.words, n_types) if bitsets else None,
                         n_compatible=int(res.n_compatible[q]), selected=int(res.selected[q]),
                         capacity_type=int(res.capacity_type[q])))
     return out

@@ -22,7 +22,9 @@ EXPORTS = ["gs_create", "gs_destroy", "gs_prepare", "gs_run", "gs_fetch", "gs_so
            "gs_batch_stats_size",
            "gs_batch_consolidate_prepare", "gs_batch_consolidate_run", "gs_batch_consolidate_fetch",
            "gs_batch_consolidate_results", "gs_batch_consolidate_error", "gs_batch_consolidate_last_run",
-           "gs_batch_consolidate_fetch_all", "gs_batch_consolidate_last_fetch", "gs_batch_fetch_stats_size"]
+           "gs_batch_consolidate_fetch_all", "gs_batch_consolidate_last_fetch", "gs_batch_fetch_stats_size",
+           "gs_create_filter_prepare", "gs_create_filter_run", "gs_create_filter_set_available",
+           "gs_create_filter_last_run", "gs_create_filter_stats_size"]
 
 
 def source_digest():
@@ -86,6 +88,17 @@ def load():
         L.gs_create_filter.argtypes = [vp, C.POINTER(abi.GsProblem), C.POINTER(abi.GsClaimQuery), C.c_uint32,
                                        C.POINTER(abi.GsClaimFilterResult)]
         L.gs_create_filter.restype = C.c_int
+        L.gs_create_filter_prepare.argtypes = [vp, C.POINTER(abi.GsProblem)]
+        L.gs_create_filter_prepare.restype = C.c_int
+        L.gs_create_filter_run.argtypes = [vp, C.POINTER(abi.GsProblem), C.POINTER(abi.GsClaimQuery), C.c_uint32,
+                                           C.c_uint32, C.POINTER(abi.GsClaimFilterResult)]
+        L.gs_create_filter_run.restype = C.c_int
+        L.gs_create_filter_set_available.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_uint32]
+        L.gs_create_filter_set_available.restype = C.c_int
+        L.gs_create_filter_last_run.argtypes = [vp, C.POINTER(abi.GsCreateFilterStats)]
+        L.gs_create_filter_last_run.restype = C.c_int
+        L.gs_create_filter_stats_size.argtypes = []
+        L.gs_create_filter_stats_size.restype = C.c_uint32
         L.gs_build_catalog.argtypes = [vp, C.POINTER(abi.GsVpcProfile), C.c_uint32, C.POINTER(abi.GsCatalogEnv),
                                        C.POINTER(abi.GsCatalog)]
         L.gs_build_catalog.restype = C.c_int
@@ -217,6 +230,7 @@ class Solver:
         self.cluster = None  # the cluster of the last consolidate (resource names of its results)
         self.batch_problems = []  # the problems of the last batch_prepare
         self.batch_clusters = []  # the clusters of the last batch_consolidate_prepare (None: no cluster)
+        self.cf_types = 0  # instance types of the last create_filter_prepare
 
     def close(self):
         if self.ctx:
@@ -417,6 +431,40 @@ class Solver:
         if raw:
             return res
         return abi.claim_filter_to_list(res, len(problem.instance_types))
+
+    # ---- the same re-filter against a catalog kept on the device
+    def create_filter_prepare(self, problem):
+        """gs_create_filter_prepare: reduce and upload problem's catalog once"""
+        self._check(self.L.gs_create_filter_prepare(self.ctx, C.byref(problem.struct)))
+        self.cf_types = len(problem.instance_types)
+
+    def create_filter_run(self, problem, bitsets=True, raw=False):
+        """gs_create_filter_run over problem.claim_queries (problem is the
+        claims' pool; its string ids need not be the catalog's) -> the list
+        create_filter returns; without bitsets `compatible` and
+        `requirements` are None"""
+        res = abi.GsClaimFilterResult()
+        self._check(self.L.gs_create_filter_run(self.ctx, C.byref(problem.struct), problem.claim_queries,
+                                                problem.n_claim_queries, abi.GS_CF_BITSETS if bitsets else 0,
+                                                C.byref(res)))
+        if raw:
+            return res
+        return abi.claim_filter_to_list(res, self.cf_types, bitsets)
+
+    def create_filter_set_available(self, indices, flags):
+        """gs_create_filter_set_available: offering indices of the prepared
+        catalog and their new Available values, applied in order"""
+        n = len(indices)
+        assert len(flags) == n
+        idx = (C.c_uint32 * max(n, 1))(*[int(i) for i in indices])
+        av = (C.c_uint8 * max(n, 1))(*[1 if f else 0 for f in flags])
+        self._check(self.L.gs_create_filter_set_available(self.ctx, idx, av, n))
+
+    def create_filter_last_run(self):
+        """gs_create_filter_last_run -> dict of the gs_create_filter_stats fields"""
+        out = abi.GsCreateFilterStats()
+        self._check(self.L.gs_create_filter_last_run(self.ctx, C.byref(out)))
+        return {name: getattr(out, name) for name, _ in abi.GsCreateFilterStats._fields_}
 
     def build_catalog(self, profiles, zones, price_rows=(), unavailable=(), now_ns=0, spot_discount_percent=0,
                       kubelet=None, raw=False, region=None):

@@ -318,6 +318,23 @@ class Problem:
         fn(self._builder)
         return Problem(self._builder)
 
+    def claims_pool(self):
+        """a new Problem that holds nothing but this one's claim queries, with
+        a string table of its own: what a caller of gs_create_filter_run sends
+        once the catalog is resident"""
+        ops = {v: k for k, v in abi.OPS.items()}
+        b = ProblemBuilder()
+        for i in range(self.n_claim_queries):
+            q = self.claim_queries[i]
+            reqs = []
+            for r in self.reqs[q.requirements.begin:q.requirements.begin + q.requirements.count]:
+                vb, vn = int(r["values"]["begin"]), int(r["values"]["count"])
+                reqs.append((self.strings[r["key"]], ops[int(r["op"])],
+                             [self.strings[v] for v in self.value_ids[vb:vb + vn]], int(r["min_values"])))
+            qty = self.quantities[q.requests.begin:q.requests.begin + q.requests.count]
+            b.add_claim_query(reqs, {self.strings[x["resource"]]: int(x["milli"]) for x in qty})
+        return b.build()
+
     @property
     def n_pods(self):
         return len(self.pods)
