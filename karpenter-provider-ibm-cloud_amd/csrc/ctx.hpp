@@ -125,11 +125,11 @@ struct Batch;  // batch.cpp: the slots of gs_batch_*
 void batch_destroy(gs_ctx* c);
 struct ConsBatch;  // batch_consolidate.hip: the slots of gs_batch_consolidate_*
 void batch_consolidate_destroy(gs_ctx* c);
-void create_filter_destroy(gs_ctx* c);  // filter.hip: the re-filter's arena and its resident catalog
+void create_filter_destroy(gs_ctx* c);  // filter.hip: frees gs_ctx::cf
 
 }  // namespace gsc
 namespace gsf {
-struct Resident;  // filter.hip: gs_create_filter_prepare's catalog and the runs' buffers
+struct State;  // filter.hip: the re-filter's arena and results, its resident catalog and the runs' buffers
 }
 
 struct gs_ctx {
@@ -196,14 +196,7 @@ struct gs_ctx {
   uint32_t* res_nits = nullptr;
   uint32_t* res_drop = nullptr;
 
-  // gs_create_filter: grow-once device arena and result storage
-  void* cf_dev = nullptr;
-  size_t cf_bytes = 0;
-  std::vector<uint64_t> cf_create, cf_reqs, cf_spot;
-  std::vector<uint32_t> cf_n, cf_ct;
-  std::vector<int32_t> cf_sel;
-  double t_filter = 0;
-  gsf::Resident* cf_res = nullptr;  // gs_create_filter_prepare / _run: separate from the arena above
+  gsf::State* cf = nullptr;  // gs_create_filter and gs_create_filter_prepare / _run (filter.hip)
   // gs_build_catalog result storage
   std::vector<std::string> cat_strs, cat_reasons;
   std::vector<const char*> cat_ptrs, cat_reason_ptrs;

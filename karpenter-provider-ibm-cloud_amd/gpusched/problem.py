@@ -288,16 +288,19 @@ class Problem:
 
     def dump(self, path):
         """binary dump read by tools/encode_harness.cpp (host-only encoder
-        runs: sanitizers, profiling)"""
+        runs: sanitizers, profiling); the claim queries follow the gs_problem
+        arrays"""
         import struct
         with open(path, "wb") as f:
-            f.write(b"GSPD" + struct.pack("<II", 4, len(self._bytes)))
+            f.write(b"GSPD" + struct.pack("<II", 5, len(self._bytes)))
             for s in self._bytes:
                 f.write(struct.pack("<I", len(s)) + s)
             for name in self._DUMP_ARRAYS:
                 a = np.ascontiguousarray(getattr(self, name))
                 f.write(struct.pack("<QQ", len(a), a.dtype.itemsize))
                 f.write(a.tobytes())
+            f.write(struct.pack("<QQ", self.n_claim_queries, C.sizeof(abi.GsClaimQuery)))
+            f.write(bytes(self.claim_queries)[:self.n_claim_queries * C.sizeof(abi.GsClaimQuery)])
 
     def with_pods(self, idx):
         """a view with pending pods pods[idx] (same pools: requirement, label

@@ -9,6 +9,13 @@ problems, consolidation clusters with bound pods — plus deliberately corrupted
 inputs (out-of-range ranges and ids), which must come back as GS_E_INVALID
 instead of reading out of bounds.  Statuses must agree with the product
 library's gs_validate (same encoder, compiled by hipcc).
+
+The Create re-filter's host side (csrc/filter_encode.cpp: the reduction of
+the caller's requirement lists; csrc/filter_rules.hpp: the rule for one
+(claim, instance type) pair that both kernels call) is in the same build:
+encode_harness -f reduces a catalog and claims as the entry points do and
+evaluates the rule on the CPU.  Its answer must be the oracle's, bit for bit,
+and corrupt ranges and ids on either side must come back as GS_E_INVALID.
 """
 import os
 import shutil
@@ -19,6 +26,8 @@ import numpy as np
 import pytest
 
 from gpusched import abi, lib, synth
+from oracle import pyoracle
+from test_create_filter import CT_CASES, GIT_CASES, _git_problem, _kat_problem, random_catalog
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "karpenter-provider-ibm-cloud_amd", "csrc")
@@ -180,3 +189,101 @@ def test_dump_roundtrip_status_matches_validate(tmp_path):
     with open(path, "rb") as f:
         assert f.read(4) == b"GSPD"
     assert os.path.getsize(path) > np.asarray(p.pods).nbytes
+
+
+# ------------------------------------------------------ the Create re-filter
+def _bits(words):
+    """'3,0,80' (hex u64 words) -> the set bit indices"""
+    if words == "-":
+        return []
+    return [64 * w + i for w, x in enumerate(words.split(",")) for i in range(64) if (int(x, 16) >> i) & 1]
+
+
+def _run_filter(harness, pairs):
+    """encode_harness -f over (catalog dump, claims dump) pairs -> per pair
+    (status, rows in pyoracle.create_filter's form); a disagreement between
+    the per-call and the prepared form is a non-zero exit"""
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([harness, "-f"] + [x for pair in pairs for x in pair], capture_output=True, text=True,
+                       timeout=900, env=env)
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+    out = []
+    for line in r.stdout.strip().split("\n"):
+        f = line.split()
+        if line.endswith(".gspd"):
+            out.append((int(f[0]), []))
+        elif f[0] != "msg":
+            n, sel, ct, create, reqs = f
+            out[-1][1].append(dict(compatible=_bits(create), requirements=_bits(reqs), n_compatible=int(n),
+                                   selected=int(sel), capacity_type=int(ct)))
+    assert len(out) == len(pairs)
+    return out
+
+
+def test_create_filter_reducer_matches_oracle_under_asan(harness, tmp_path):
+    """the reducer and pair_verdict against the oracle, in the prepared form
+    and (same file on both sides) in the per-call form too"""
+    probs = [(f"cat{s}", random_catalog(s, 150, 40)) for s in range(6)]
+    probs += [(f"ct{i}", _kat_problem(c)) for i, c in enumerate(CT_CASES)]
+    probs += [(f"git{i}", _git_problem(c)) for i, c in enumerate(GIT_CASES)]
+    pairs, want = [], []
+    for name, p in probs:
+        path = str(tmp_path / f"{name}.gspd")
+        p.dump(path)
+        pairs.append((path, path))
+        want.append(pyoracle.create_filter(p))
+    # the claims in a pool of their own (other string ids) against the first catalog
+    pool = str(tmp_path / "pool.gspd")
+    probs[0][1].claims_pool().dump(pool)
+    pairs.append((pairs[0][0], pool))
+    want.append(want[0])
+    # the inputs are not trivial: some claim keeps no type, some claim keeps several
+    kept = [q["n_compatible"] for st, rows in want[:6] for q in rows]
+    assert 0 in kept and max(kept) > 1
+    got = _run_filter(harness, pairs)
+    for (cat, claims), (st, rows), (wst, wrows) in zip(pairs, got, want):
+        assert wst == abi.GS_OK and st == wst, (cat, claims, st)
+        assert rows == wrows, (cat, claims)
+
+
+def _corrupt_filter(kind):
+    p = random_catalog(3, 30, 8)
+    it0 = p.instance_types[0]
+    if kind == "req_key_id":
+        p.reqs["key"][it0["requirements"]["begin"]] = len(p.strings) + 100
+    elif kind == "value_range":
+        p.reqs["values"]["count"][it0["requirements"]["begin"]] = 1 << 30
+    elif kind == "quantity_resource_id":
+        p.quantities["resource"][it0["capacity"]["begin"]] = len(p.strings) + 7
+    elif kind == "it_offerings_range":
+        p.instance_types["offerings"]["begin"][0] = len(p.offerings)
+        p.instance_types["offerings"]["count"][0] = 3
+    elif kind == "claim_reqs_range":
+        p.claim_queries[0].requirements.count = len(p.reqs) + 1
+    elif kind == "claim_requests_range":
+        p.claim_queries[0].requests.begin = len(p.quantities) + 2
+        p.claim_queries[0].requests.count = 1
+    elif kind == "claim_gt_not_integer":
+        p = p.extended(lambda b: b.add_claim_query([("karpenter-ibm.sh/instance-cpu", "Gt", ["x"])]))
+    return p
+
+
+CORRUPT_FILTER = ["req_key_id", "value_range", "quantity_resource_id", "it_offerings_range", "claim_reqs_range",
+                  "claim_requests_range", "claim_gt_not_integer"]
+
+
+def test_create_filter_reducer_rejects_corrupt_inputs_under_asan(harness, tmp_path):
+    pairs = []
+    for kind in CORRUPT_FILTER:
+        path = str(tmp_path / f"{kind}.gspd")
+        _corrupt_filter(kind).dump(path)
+        pairs.append((path, path))
+    # the claims' side alone, against a sound catalog
+    sound = str(tmp_path / "sound.gspd")
+    random_catalog(3, 30, 8).dump(sound)
+    pairs += [(sound, path) for (path, _), kind in zip(pairs, CORRUPT_FILTER) if kind.startswith("claim_")]
+    got = _run_filter(harness, pairs)
+    assert got[-1][0] == abi.GS_E_INVALID and len(got) == len(CORRUPT_FILTER) + 3
+    for (cat, claims), (st, rows) in zip(pairs, got):
+        assert st == abi.GS_E_INVALID and not rows, (cat, claims, st)

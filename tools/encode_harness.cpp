@@ -1,5 +1,6 @@
 // encode_harness.cpp — host-only driver of the Solve encoder (encode.cpp and
 // the units it drives: vocab, catalog, taints, pods, nodes, topology, reqs, par)
+// and of the Create re-filter's host side (filter_encode.cpp, filter_rules.hpp)
 // over gs_problem dumps written by gpusched.problem.Problem.dump().
 // Built with g++ (no HIP) for three uses:
 //  * sanitizers: tests/test_encode_sanitizers.py builds it with
@@ -10,6 +11,19 @@
 // Usage: encode_harness [-n reps] [-d] dump...   prints "<status> <ms> <path>"
 // per dump; with -d then the message, one "<array> <length> <FNV-1a 64>" line
 // per Encoded array and one "host" line over the host-only decode state.
+//
+// encode_harness -f catalog.gspd claims.gspd ...   (pairs) is the Create
+// re-filter on the CPU: the first dump's catalog and the second dump's claim
+// queries are reduced as gs_create_filter_prepare and gs_create_filter_run
+// reduce them (the claims against the catalog's vocabularies, with call-local
+// ids and the catalog's resource columns), laid out by the same two images,
+// and pair_verdict — the rule both kernels call — is evaluated for every
+// (claim, instance type) pair.  Where both paths name one file the per-call
+// form of gs_create_filter (one reduction, claims first) runs too, and any
+// bit the two forms disagree on makes the exit status 3.  Prints
+// "<status> <catalog> <claims>" per pair and then the message of a refusal or, per claim,
+// "<n_compatible> <selected> <capacity_type> <Create words> <requirements words>"
+// (bitset words in hex, comma-separated, "-" for a catalog without types).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -18,6 +32,7 @@
 #include <vector>
 
 #include "../karpenter-provider-ibm-cloud_amd/csrc/encode.hpp"
+#include "../karpenter-provider-ibm-cloud_amd/csrc/filter_encode.hpp"
 
 namespace {
 
@@ -26,19 +41,21 @@ struct Dump {
   std::vector<const char*> ptrs;
   std::vector<std::vector<char>> arrays;
   gs_problem p{};
+  const gs_claim_query* queries = nullptr;
+  uint32_t n_queries = 0;
 };
 
 bool read_exact(FILE* f, void* dst, size_t n) { return fread(dst, 1, n, f) == n; }
 
-// layout: magic "GSPD", u32 version 4, u32 n_strings, per string u32 len +
-// bytes, then 21 arrays in gs_problem order (value_ids .. namespaces),
-// each u64 count + u64 element size + raw bytes
+// layout: magic "GSPD", u32 version 5, u32 n_strings, per string u32 len +
+// bytes, then 21 arrays in gs_problem order (value_ids .. namespaces) and the
+// claim queries, each u64 count + u64 element size + raw bytes
 bool load(const char* path, Dump& d) {
   FILE* f = fopen(path, "rb");
   if (!f) return false;
   char magic[4];
   uint32_t ver = 0, ns = 0;
-  bool ok = read_exact(f, magic, 4) && memcmp(magic, "GSPD", 4) == 0 && read_exact(f, &ver, 4) && ver == 4 &&
+  bool ok = read_exact(f, magic, 4) && memcmp(magic, "GSPD", 4) == 0 && read_exact(f, &ver, 4) && ver == 5 &&
             read_exact(f, &ns, 4);
   for (uint32_t i = 0; ok && i < ns; i++) {
     uint32_t len = 0;
@@ -47,7 +64,7 @@ bool load(const char* path, Dump& d) {
     ok = ok && (len == 0 || read_exact(f, &s[0], len));
     d.strs.push_back(std::move(s));
   }
-  for (int a = 0; ok && a < 21; a++) {
+  for (int a = 0; ok && a < 22; a++) {
     uint64_t n = 0, es = 0;
     ok = read_exact(f, &n, 8) && read_exact(f, &es, 8);
     std::vector<char> buf(n * es);
@@ -83,6 +100,7 @@ bool load(const char* path, Dump& d) {
   p.volumes = (const gs_volume*)A(18), p.n_volumes = N(18, sizeof(gs_volume));
   p.volume_limits = (const gs_volume_limit*)A(19), p.n_volume_limits = N(19, sizeof(gs_volume_limit));
   p.namespaces = (const gs_namespace*)A(20), p.n_namespaces = N(20, sizeof(gs_namespace));
+  d.queries = (const gs_claim_query*)A(21), d.n_queries = N(21, sizeof(gs_claim_query));
   return true;
 }
 
@@ -148,12 +166,209 @@ void digest(const gsh::Err& er, const gsh::Encoded& e) {
   printf("  host %zu %zu %016llx\n", e.tmpl_reqs.size(), e.variants.size(), (unsigned long long)f.h);
 }
 
+// ------------------------------------------------ the Create re-filter (-f)
+using namespace gsf;
+
+// what DevSelect is on the device: the catalog's image and the claims' image
+// under host addresses.  Dense value ids below V are the catalog's.
+struct HostView {
+  const FReq* reqs;
+  const uint32_t* vals;
+  const int64_t* vint;
+  const uint8_t* vok;
+  const FIt* its;
+  const FOff* offs;
+  const int64_t* alloc;
+  uint32_t N, R, V;
+  const FReq* q_reqs;
+  const uint32_t* q_vals;
+  const int64_t* q_vint;
+  const uint8_t* q_vok;
+  const FQuery* qs;
+  const FQty* qty;
+  bool vok_at(uint32_t v) const { return v < V ? vok[v] : q_vok[v - V]; }
+  int64_t vint_at(uint32_t v) const { return v < V ? vint[v] : q_vint[v - V]; }
+};
+
+struct Verdicts {
+  gs_status status = GS_OK;
+  std::string msg;
+  uint32_t W = 0;
+  std::vector<uint64_t> create, reqs, spot;  // [Q][W]
+  std::vector<uint32_t> n, ct;
+  std::vector<int32_t> sel;
+  bool operator==(const Verdicts& o) const {
+    return status == o.status && W == o.W && create == o.create && reqs == o.reqs && spot == o.spot && n == o.n &&
+           ct == o.ct && sel == o.sel;
+  }
+};
+
+// pair_verdict over every pair, folded as the kernels and their callers fold it
+void evaluate(const HostView& d, uint32_t nq, Verdicts& out) {
+  const uint32_t W = (d.N + 63) / 64;
+  out.W = W;
+  out.create.assign((size_t)nq * W, 0);
+  out.reqs.assign((size_t)nq * W, 0);
+  out.spot.assign((size_t)nq * W, 0);
+  out.n.assign(nq, 0);
+  out.sel.assign(nq, -1);
+  out.ct.assign(nq, GS_CAPACITY_ON_DEMAND);
+  for (uint32_t q = 0; q < nq; q++) {
+    const FQuery Q = d.qs[q];
+    bool spot = false;
+    for (uint32_t it = 0; it < d.N; it++) {
+      const uint32_t ok = pair_verdict(d, Q, d.q_reqs + Q.reqs.b, d.q_vals, d.reqs, d.vals, it);
+      const size_t w = (size_t)q * W + (it >> 6);
+      const uint64_t bit = 1ull << (it & 63);
+      if (ok & P_REQS) out.reqs[w] |= bit;
+      if (ok & P_CREATE) {
+        out.create[w] |= bit;
+        if (out.sel[q] < 0) out.sel[q] = (int32_t)it;
+        out.n[q]++;
+      }
+      if (ok & P_SPOT) out.spot[w] |= bit, spot = true;
+    }
+    if (Q.spot && spot) out.ct[q] = GS_CAPACITY_SPOT;
+  }
+}
+
+// gs_create_filter_prepare on cat, then gs_create_filter_run of pool's claims
+Verdicts filter_prepared(const gs_problem* cat, const gs_problem* pool, const gs_claim_query* qs, uint32_t nq) {
+  Verdicts out;
+  if (null_with_count(cat, true) || null_with_count(pool, false)) {
+    out.status = GS_E_INVALID;
+    return out;
+  }
+  try {
+    Enc ce;
+    ce.p = cat;
+    Columns cc;
+    std::vector<FIt> its;
+    std::vector<FOff> offs;
+    std::vector<int64_t> alloc;
+    capacity_columns(ce, cc);
+    encode_catalog(ce, cc.id, cc.R, its, offs, alloc, nullptr);
+    Image ci;
+    const CatalogImage cimg(ci, ce, its, offs, alloc);
+    std::vector<char> hc(ci.off);
+    cimg.fill(hc.data(), ce, its, offs, alloc);
+    // ids for this call only, above the catalog's
+    Enc e;
+    e.p = pool;
+    e.base = &ce;
+    e.kb = (uint32_t)ce.key_name.size();
+    e.vb = (uint32_t)ce.vint.size();
+    Columns cols;
+    cols.catalog = &cc;
+    std::vector<FQuery> fq;
+    std::vector<FQty> qty;
+    encode_claims(e, qs, nq, resident_column, cols, fq, qty);
+    Image qi;
+    const ClaimImage qimg(qi, &e, fq, qty);
+    std::vector<char> hq(qi.off);
+    qimg.fill(hq.data(), &e, fq, qty);
+    HostView d{};
+    cimg.bind(hc.data(), d);
+    qimg.bind(hq.data(), d);
+    qimg.bind_lists(hq.data(), d);
+    d.N = cat->n_instance_types;
+    d.R = cc.R;
+    d.V = e.vb;
+    evaluate(d, nq, out);
+  } catch (const Fail& f) {
+    out.status = f.code;
+    out.msg = f.msg;
+  }
+  return out;
+}
+
+// gs_create_filter: one reduction (claims first), one arena
+Verdicts filter_per_call(const gs_problem* p, const gs_claim_query* qs, uint32_t nq) {
+  Verdicts out;
+  if (null_with_count(p, true)) {
+    out.status = GS_E_INVALID;
+    return out;
+  }
+  try {
+    Enc e;
+    e.p = p;
+    Columns cols;
+    std::vector<FIt> its;
+    std::vector<FOff> offs;
+    std::vector<FQuery> fq;
+    std::vector<FQty> qty;
+    std::vector<int64_t> alloc;
+    encode_claims(e, qs, nq, call_column, cols, fq, qty);
+    const uint32_t R = std::max<uint32_t>(1, (uint32_t)cols.id.size());
+    encode_catalog(e, cols.id, R, its, offs, alloc, nullptr);
+    Image im;
+    const CatalogImage cat(im, e, its, offs, alloc);
+    const ClaimImage claims(im, nullptr, fq, qty);
+    std::vector<char> h(im.off);
+    cat.fill(h.data(), e, its, offs, alloc);
+    claims.fill(h.data(), nullptr, fq, qty);
+    HostView d{};
+    cat.bind(h.data(), d);
+    claims.bind(h.data(), d);
+    d.q_reqs = d.reqs;  // one Enc: the claims' lists and values are the catalog image's
+    d.q_vals = d.vals;
+    d.N = p->n_instance_types;
+    d.R = R;
+    d.V = ~0u;
+    evaluate(d, nq, out);
+  } catch (const Fail& f) {
+    out.status = f.code;
+    out.msg = f.msg;
+  }
+  return out;
+}
+
+void print_words(const uint64_t* w, uint32_t n) {
+  if (!n) printf("-");
+  for (uint32_t i = 0; i < n; i++) printf("%s%llx", i ? "," : "", (unsigned long long)w[i]);
+}
+
+int filter_main(int argc, char** argv, int i) {
+  int rc = 0;
+  for (; i + 1 < argc; i += 2) {
+    Dump cat, claims;
+    if (!load(argv[i], cat) || !load(argv[i + 1], claims)) {
+      fprintf(stderr, "cannot read %s or %s\n", argv[i], argv[i + 1]);
+      rc = 2;
+      continue;
+    }
+    const Verdicts v = filter_prepared(&cat.p, &claims.p, claims.queries, claims.n_queries);
+    if (strcmp(argv[i], argv[i + 1]) == 0 && !(filter_per_call(&cat.p, cat.queries, cat.n_queries) == v)) {
+      fprintf(stderr, "%s: the per-call and the prepared form disagree\n", argv[i]);
+      rc = 3;
+    }
+    printf("%d %s %s\n", (int)v.status, argv[i], argv[i + 1]);
+    if (v.status != GS_OK) {
+      printf("  msg %s\n", v.msg.c_str());
+      continue;
+    }
+    for (uint32_t q = 0; q < claims.n_queries; q++) {
+      printf("%u %d %u ", v.n[q], v.sel[q], v.ct[q]);
+      print_words(v.create.data() + (size_t)q * v.W, v.W);
+      printf(" ");
+      print_words(v.reqs.data() + (size_t)q * v.W, v.W);
+      printf("\n");
+    }
+  }
+  if (i < argc) {
+    fprintf(stderr, "-f takes pairs of dumps\n");
+    rc = 2;
+  }
+  return rc;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   int reps = 1, i = 1;
   bool dump = false;
   for (; i < argc && argv[i][0] == '-'; i++) {
+    if (strcmp(argv[i], "-f") == 0) return filter_main(argc, argv, i + 1);
     if (strcmp(argv[i], "-d") == 0) dump = true;
     else if (strcmp(argv[i], "-n") == 0 && i + 1 < argc) reps = atoi(argv[++i]);
     else break;
