@@ -710,6 +710,78 @@ gs_status gs_rank_instance_types(uint32_t n, const int64_t* cpu_milli, const int
                                  int64_t min_memory_gb, double max_price, uint32_t* out_order, uint32_t* out_n,
                                  double* out_score);
 
+/* ---- the same ranking against a catalog kept on the device ---------------
+ * The autoplacement controller ranks once per IBMNodeClass
+ * (pkg/controllers/nodeclass/autoplacement/controller.go:104-163 ->
+ * FilterInstanceTypes, instancetype.go:259-379): every NodeClass of a region
+ * ranks the same catalog with its own four filter values.
+ * calculateInstanceTypeScore (:90-110) reads only the type, so a prepare
+ * uploads the four columns once and keeps, per type, the float64 score and a
+ * u16 order key (how many catalog scores are strictly below it); a run ranks
+ * many queries in one launch, one workgroup per query, and sends nothing of
+ * the catalog.  The resident catalog is separate from gs_rank_instance_types
+ * and from the other resident state of the context: none uses or disturbs
+ * another. */
+#define GS_RANK_BATCH_MAX 4096u /* queries per run */
+#define GS_RANK_SCORES 1u       /* run flag: return the ranked scores as well */
+/* One NodeClass's filters, with the meaning of gs_rank_instance_types'
+ * arguments of the same names (GS_ARCH_ANY, values <= 0 and a NaN max_price
+ * switch a filter off).  32 bytes, no padding; `reserved` is not read. */
+typedef struct gs_rank_query {
+  int64_t min_cpu;       /* :326 */
+  int64_t min_memory_gb; /* :331-335 */
+  double max_price;      /* :339 (the parsed MaximumHourlyPrice) */
+  uint32_t want_arch;    /* :321 */
+  uint32_t reserved;
+} gs_rank_query;
+/* Results of a run, owned by the ctx until the next run, prepare or
+ * gs_destroy.  Row i of `order` holds the first min(n_kept[i], stride) List
+ * indices of query i's ranking (rankInstanceTypes :358-379, ties as Go's
+ * sort.Slice leaves them); the rest of the row is unspecified. */
+typedef struct gs_rank_result {
+  uint32_t n_queries;
+  uint32_t stride;         /* max_out ? min(max_out, n types) : n types */
+  const uint32_t* n_kept;  /* [n_queries] every type the filters keep, also beyond stride */
+  const uint32_t* order;   /* [n_queries][stride] */
+  const double* score;     /* [n_queries][stride] under GS_RANK_SCORES, else NULL (and not transferred) */
+} gs_rank_result;
+/* counters and times of the last prepare or run */
+typedef struct gs_rank_stats {
+  double encode_ms;   /* host: the checks and the upload image (prepare), the query image (run) */
+  double upload_ms;   /* host clock: prepare: allocation + transfer + rank_prepare_kernel, waited for; run:
+                         enqueueing the transfer and the launch */
+  double kernel_ms;   /* HIP events: rank_prepare_kernel (prepare), rank_batch_kernel (run) */
+  double fetch_ms;    /* run, host clock: the copy back and waiting for the device */
+  uint64_t h2d_bytes; /* prepare: 28 per type; run: 32 per query, nothing of the catalog */
+  uint64_t d2h_bytes; /* run: per query 4 + 4 * stride, 4 + 12 * stride under GS_RANK_SCORES */
+  uint32_t n_launches;
+  uint32_t n_queries;
+  uint32_t n_instance_types;
+  uint32_t reserved;
+} gs_rank_stats;
+/* Upload the catalog (the columns of gs_rank_instance_types, same checks and
+ * statuses: negative quantities or a NaN price GS_E_INVALID, n > GS_RANK_MAX
+ * GS_E_CAPACITY) and compute every type's score and order key on the device.
+ * The checks happen on the host before the device is touched: a prepare that
+ * fails leaves the previous resident catalog answering.  n = 0 is valid.  A
+ * second prepare (a catalog list or a pricing refresh) replaces the first.
+ * Runs on the ctx's device and stream. */
+gs_status gs_rank_prepare(gs_ctx* ctx, uint32_t n, const int64_t* cpu_milli, const int64_t* memory_bytes,
+                          const double* price, const uint32_t* arch);
+/* Rank nq queries against the resident catalog in one launch.  max_out = 0
+ * returns every kept type; otherwise rows hold the top min(max_out, n).
+ * flags: 0 or GS_RANK_SCORES.  GS_E_INVALID: no resident catalog, a null q
+ * with nq > 0, an unknown flag; GS_E_CAPACITY: nq > GS_RANK_BATCH_MAX; the
+ * resident catalog stays usable after either.  nq = 0 is valid.  A query has
+ * no refusable form, so there is no per-query status. */
+gs_status gs_rank_run(gs_ctx* ctx, const gs_rank_query* q, uint32_t nq, uint32_t max_out, uint32_t flags,
+                      gs_rank_result* out);
+gs_status gs_rank_last_run(const gs_ctx* ctx, gs_rank_stats* out);
+/* sizeof the three structs, for a binding's layout check */
+uint32_t gs_rank_query_size(void);
+uint32_t gs_rank_result_size(void);
+uint32_t gs_rank_stats_size(void);
+
 /* ------------------------------------------------ launch-time re-filter
  * One NodeClaim as CloudProvider.Create sees it (reference
  * pkg/cloudprovider/cloudprovider.go:284-346): spec.requirements and

@@ -126,10 +126,14 @@ void batch_destroy(gs_ctx* c);
 struct ConsBatch;  // batch_consolidate.hip: the slots of gs_batch_consolidate_*
 void batch_consolidate_destroy(gs_ctx* c);
 void create_filter_destroy(gs_ctx* c);  // filter.hip: frees gs_ctx::cf
+void rank_batch_destroy(gs_ctx* c);     // rank_batch.hip: frees gs_ctx::rank
 
 }  // namespace gsc
 namespace gsf {
 struct State;  // filter.hip: the re-filter's arena and results, its resident catalog and the runs' buffers
+}
+namespace gsrb {
+struct State;  // rank_batch.hip: the ranking's resident catalog and the runs' buffers
 }
 
 struct gs_ctx {
@@ -197,6 +201,7 @@ struct gs_ctx {
   uint32_t* res_drop = nullptr;
 
   gsf::State* cf = nullptr;  // gs_create_filter and gs_create_filter_prepare / _run (filter.hip)
+  gsrb::State* rank = nullptr;  // gs_rank_prepare / _run (rank_batch.hip)
   // gs_build_catalog result storage
   std::vector<std::string> cat_strs, cat_reasons;
   std::vector<const char*> cat_ptrs, cat_reason_ptrs;

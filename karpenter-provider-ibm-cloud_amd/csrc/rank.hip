@@ -25,6 +25,9 @@
 #include <vector>
 
 #include "../../include/gpusched.h"
+#include "rank_rules.hpp"
+
+static_assert(gsr::kArchAny == GS_ARCH_ANY, "rank_rules.hpp arch wildcard");
 
 namespace {
 
@@ -63,19 +66,9 @@ __global__ __launch_bounds__(RK_NT) void rank_kernel(RankArgs a) {
     if (i < a.n) {
       const int64_t cm = a.cpu_milli[i], mb = a.memory_bytes[i];
       const double p = a.price[i];
-      // Capacity.Cpu().Value() and Memory().ScaledValue(Giga) round up
-      const int64_t cpu = (cm + 999) / 1000;
-      const int64_t mem_gb = (mb + 999999999) / 1000000000;
-      keep = (a.want_arch == GS_ARCH_ANY || a.arch[i] == a.want_arch) && (a.min_cpu <= 0 || cpu >= a.min_cpu) &&
-             (a.min_memory_gb <= 0 || !((double)mb / 1073741824.0 < (double)a.min_memory_gb)) &&
-             (!(a.max_price > 0) || !(p > a.max_price));
-      if (p <= 0) {
-        s = (double)cpu + (double)mem_gb;
-      } else {
-        const double ce = p / (double)cpu;
-        const double me = p / (double)mem_gb;
-        s = (ce + me) / 2;
-      }
+      // the filters and the score: rank_rules.hpp
+      keep = gsr::keep(cm, mb, p, a.arch[i], a.want_arch, a.min_cpu, a.min_memory_gb, a.max_price);
+      s = gsr::score(cm, mb, p);
     }
     const uint64_t b = __ballot(keep);
     if (lane == 0) wcnt[wave] = (uint32_t)__popcll(b);

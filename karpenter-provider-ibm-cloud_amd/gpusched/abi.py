@@ -459,3 +459,39 @@ def call_rank(fn, cpu_milli, memory_bytes, price, arch, want_arch=GS_ARCH_ANY, m
             p(score, C.c_double))
     k = kept.value
     return st, order[:k].tolist(), score[:k].tolist()
+
+
+# gs_rank_prepare / gs_rank_run: the same ranking against a resident catalog
+GS_RANK_BATCH_MAX = 4096
+GS_RANK_SCORES = 1      # gs_rank_run flag: return the ranked scores as well
+
+
+class GsRankQuery(C.Structure):
+    """gs_rank_query (size checked against gs_rank_query_size)"""
+    _fields_ = [("min_cpu", C.c_int64), ("min_memory_gb", C.c_int64), ("max_price", C.c_double),
+                ("want_arch", _U32), ("reserved", _U32)]
+
+
+class GsRankResult(C.Structure):
+    """gs_rank_result (size checked against gs_rank_result_size)"""
+    _fields_ = [("n_queries", _U32), ("stride", _U32), ("n_kept", C.POINTER(C.c_uint32)),
+                ("order", C.POINTER(C.c_uint32)), ("score", C.POINTER(C.c_double))]
+
+
+class GsRankStats(C.Structure):
+    """gs_rank_stats (gs_rank_last_run; size checked against gs_rank_stats_size)"""
+    _fields_ = [("encode_ms", C.c_double), ("upload_ms", C.c_double), ("kernel_ms", C.c_double),
+                ("fetch_ms", C.c_double), ("h2d_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64),
+                ("n_launches", _U32), ("n_queries", _U32), ("n_instance_types", _U32), ("reserved", _U32)]
+
+
+def rank_queries(queries):
+    """[dict(want_arch=, min_cpu=, min_memory_gb=, max_price=)] (the keyword
+    arguments of call_rank, each optional) -> a gs_rank_query array"""
+    arr = (GsRankQuery * max(len(queries), 1))()
+    for x, kw in zip(arr, queries):
+        x.want_arch = kw.get("want_arch", GS_ARCH_ANY)
+        x.min_cpu = int(kw.get("min_cpu", 0))
+        x.min_memory_gb = int(kw.get("min_memory_gb", 0))
+        x.max_price = float(kw.get("max_price", 0.0))
+    return arr

@@ -24,7 +24,9 @@ EXPORTS = ["gs_create", "gs_destroy", "gs_prepare", "gs_run", "gs_fetch", "gs_so
            "gs_batch_consolidate_results", "gs_batch_consolidate_error", "gs_batch_consolidate_last_run",
            "gs_batch_consolidate_fetch_all", "gs_batch_consolidate_last_fetch", "gs_batch_fetch_stats_size",
            "gs_create_filter_prepare", "gs_create_filter_run", "gs_create_filter_set_available",
-           "gs_create_filter_last_run", "gs_create_filter_stats_size"]
+           "gs_create_filter_last_run", "gs_create_filter_stats_size",
+           "gs_rank_prepare", "gs_rank_run", "gs_rank_last_run", "gs_rank_query_size", "gs_rank_result_size",
+           "gs_rank_stats_size"]
 
 
 def source_digest():
@@ -104,6 +106,16 @@ def load():
         L.gs_build_catalog.restype = C.c_int
         L.gs_rank_instance_types.argtypes = abi.RANK_ARGTYPES
         L.gs_rank_instance_types.restype = C.c_int
+        L.gs_rank_prepare.argtypes = [vp] + abi.RANK_ARGTYPES[:5]
+        L.gs_rank_prepare.restype = C.c_int
+        L.gs_rank_run.argtypes = [vp, C.POINTER(abi.GsRankQuery), C.c_uint32, C.c_uint32, C.c_uint32,
+                                  C.POINTER(abi.GsRankResult)]
+        L.gs_rank_run.restype = C.c_int
+        L.gs_rank_last_run.argtypes = [vp, C.POINTER(abi.GsRankStats)]
+        L.gs_rank_last_run.restype = C.c_int
+        for name in ("gs_rank_query_size", "gs_rank_result_size", "gs_rank_stats_size"):
+            getattr(L, name).argtypes = []
+            getattr(L, name).restype = C.c_uint32
         L.gs_last_error.argtypes = [vp, C.c_char_p, C.c_size_t]
         L.gs_last_error.restype = C.c_size_t
         L.gs_version.argtypes = []
@@ -459,6 +471,47 @@ class Solver:
         idx = (C.c_uint32 * max(n, 1))(*[int(i) for i in indices])
         av = (C.c_uint8 * max(n, 1))(*[1 if f else 0 for f in flags])
         self._check(self.L.gs_create_filter_set_available(self.ctx, idx, av, n))
+
+    def rank_prepare(self, cpu_milli, memory_bytes, price, arch):
+        """gs_rank_prepare: upload the catalog's four columns once; the
+        scores and order keys are computed and kept on the device"""
+        import numpy as np
+        n = len(cpu_milli)
+        cols = [np.ascontiguousarray(a, dtype=t) for a, t in ((cpu_milli, np.int64), (memory_bytes, np.int64),
+                                                              (price, np.float64), (arch, np.uint32))]
+        ptrs = [a.ctypes.data_as(t) for a, t in zip(cols, abi.RANK_ARGTYPES[1:5])]
+        self._check(self.L.gs_rank_prepare(self.ctx, n, *ptrs))
+
+    def rank_run(self, queries, max_out=0, scores=False, raw=False):
+        """gs_rank_run over queries (a list of dicts with the keyword
+        arguments of rank_instance_types, or a gs_rank_query array with its
+        length as a pair) -> (orders, scores | None, n_kept): per query the
+        first min(n_kept, stride) ranked List indices (and their scores);
+        raw=True returns the gs_rank_result (library memory) instead"""
+        import numpy as np
+        arr, nq = queries if isinstance(queries, tuple) else (abi.rank_queries(queries), len(queries))
+        res = abi.GsRankResult()
+        self._check(self.L.gs_rank_run(self.ctx, arr, nq, max_out, abi.GS_RANK_SCORES if scores else 0,
+                                       C.byref(res)))
+        if raw:
+            return res
+        stride = res.stride
+        kept = np.ctypeslib.as_array(res.n_kept, (nq,)).copy() if nq else np.zeros(0, np.uint32)
+        if nq and stride:
+            order = np.ctypeslib.as_array(res.order, (nq, stride))
+            sc = np.ctypeslib.as_array(res.score, (nq, stride)) if scores else None
+        else:
+            order = np.zeros((nq, 0), np.uint32)
+            sc = np.zeros((nq, 0), np.float64) if scores else None
+        orders = [order[i, :min(int(kept[i]), stride)].tolist() for i in range(nq)]
+        out_scores = [sc[i, :min(int(kept[i]), stride)].tolist() for i in range(nq)] if scores else None
+        return orders, out_scores, kept.tolist()
+
+    def rank_last_run(self):
+        """gs_rank_last_run -> dict of the gs_rank_stats fields"""
+        out = abi.GsRankStats()
+        self._check(self.L.gs_rank_last_run(self.ctx, C.byref(out)))
+        return {name: getattr(out, name) for name, _ in abi.GsRankStats._fields_ if name != "reserved"}
 
     def create_filter_last_run(self):
         """gs_create_filter_last_run -> dict of the gs_create_filter_stats fields"""
