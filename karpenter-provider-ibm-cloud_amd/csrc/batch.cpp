@@ -202,7 +202,7 @@ gs_status gs_batch_prepare(gs_ctx* c, const gs_problem* const* problems, uint32_
     for (auto& t : th) t.join();
   }
   // upload the accepted slots, then gather every slot's first-pass queue
-  // records in one pair of launches
+  // records in one launch
   uint32_t accepted = 0;
   try {
     HIPCHK(hipSetDevice(c->device));

@@ -76,13 +76,12 @@ extern "C" hipError_t gsk_init_state_batch(const DevProblem* ds, uint32_t n, hip
   return hipGetLastError();
 }
 
-// the first-pass queue records of n problems (after their uploads): two launches
+// the first-pass queue records of n problems (after their uploads): one launch
 extern "C" hipError_t gsk_queue_records_batch(const DevProblem* ds, uint32_t n, uint32_t max_pods, hipStream_t s) {
   if (!n || !max_pods) return hipSuccess;
   if (n > 65535) return hipErrorInvalidValue;
   const uint32_t blocks = (max_pods + 255) / 256;
   hipLaunchKernelGGL(queue_records_kernel_batch, dim3(blocks, n), dim3(256), 0, s, ds);
-  hipLaunchKernelGGL(queue_runs_kernel_batch, dim3(blocks, n), dim3(256), 0, s, ds);
   return hipGetLastError();
 }
 

@@ -131,6 +131,5 @@ extern "C" hipError_t gsk_ffd(const DevProblem* d, uint32_t blocks, hipStream_t 
 extern "C" hipError_t gsk_queue_records(const DevProblem* d, hipStream_t s) {
   if (!d->P) return hipSuccess;
   hipLaunchKernelGGL(queue_records_kernel, dim3((d->P + 255) / 256), dim3(256), 0, s, *d);
-  hipLaunchKernelGGL(queue_runs_kernel, dim3((d->P + 255) / 256), dim3(256), 0, s, *d);
   return hipGetLastError();
 }

@@ -8,6 +8,7 @@
 
 #include "devutil.hpp"
 #include "layout.hpp"
+#include "qcode.hpp"  // qcode_floor / qcode_ceil / qcode_value
 
 namespace gsd {
 namespace {
@@ -314,6 +315,10 @@ __device__ __forceinline__ uint32_t rlane(uint32_t x, uint32_t i) {
   return (uint32_t)__builtin_amdgcn_readlane((int)x, (int)i);
 }
 
+// wave vote: the comparison's own lane mask (__ballot goes through an int per
+// lane and a second compare)
+__device__ __forceinline__ uint64_t ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+
 __device__ __forceinline__ uint32_t ffs64(uint64_t m) { return (uint32_t)__ffsll((long long)m) - 1u; }
 
 
@@ -402,9 +407,9 @@ struct RegSort {
     const uint32_t p = key(a), k = v & 0xFFFFu;
     const bool inr = (int)lane > a && (int)lane < b;
     const bool lt = k < p;
-    const int mid = a + (int)__popcll(__ballot(inr && lt));
+    const int mid = a + (int)__popcll(ballot64(inr && lt));
     const bool inl = (int)lane > a && (int)lane <= mid;
-    const uint64_t lm = __ballot(inl && !lt), rm = __ballot(inr && !inl && lt);
+    const uint64_t lm = ballot64(inl && !lt), rm = ballot64(inr && !inl && lt);
     if (lm) swap_misplaced(lm, rm);
     swap(mid, a);
     *already = lm == 0;
@@ -415,9 +420,9 @@ struct RegSort {
     const uint32_t p = key(a), k = v & 0xFFFFu;
     const bool inr = (int)lane > a && (int)lane < b;
     const bool le = k <= p;
-    const int mid = a + (int)__popcll(__ballot(inr && le));
+    const int mid = a + (int)__popcll(ballot64(inr && le));
     const bool inl = (int)lane > a && (int)lane <= mid;
-    const uint64_t lm = __ballot(inl && !le), rm = __ballot(inr && !inl && le);
+    const uint64_t lm = ballot64(inl && !le), rm = ballot64(inr && !inl && le);
     if (lm) swap_misplaced(lm, rm);
     return mid + 1;
   }
@@ -444,7 +449,7 @@ struct RegSort {
     for (int j = 0; j < 5; j++) {
       const uint32_t k = v & 0xFFFFu;
       const uint32_t pk = (uint32_t)__shfl((int)v, (int)lane - 1) & 0xFFFFu;
-      const uint64_t inv = __ballot((int)lane >= i && (int)lane < b && k < pk);
+      const uint64_t inv = ballot64((int)lane >= i && (int)lane < b && k < pk);
       if (!inv) return true;
       i = (int)ffs64(inv);
       if (b - a < 50) return false;
@@ -452,14 +457,14 @@ struct RegSort {
       if (i - a >= 2) {
         // the smaller element (at i - 1) passes the strictly greater ones
         const uint32_t x = key(i - 1);
-        const uint64_t hm = __ballot((int)lane <= i - 2 && (v & 0xFFFFu) <= x);
+        const uint64_t hm = ballot64((int)lane <= i - 2 && (v & 0xFFFFu) <= x);
         const int q = hm ? 63 - (int)__clzll((long long)hm) : -1;
         rotate_up(q + 1, i - 1);
       }
       if (b - i >= 2) {
         // the greater element (at i) passes the strictly smaller ones
         const uint32_t y = key(i);
-        const uint64_t em = __ballot((int)lane > i && (int)lane < b && (v & 0xFFFFu) >= y);
+        const uint64_t em = ballot64((int)lane > i && (int)lane < b && (v & 0xFFFFu) >= y);
         const int e = em ? (int)ffs64(em) : b;
         rotate_down(i, e - 1);
       }
@@ -676,14 +681,14 @@ __device__ __forceinline__ uint32_t wave_first(uint32_t lo, uint32_t hi, uint32_
   while (hi - lo > 64) {
     const uint32_t step = (hi - lo + 63) / 64;
     const uint32_t k = lo + lane * step + step - 1;  // last index of this lane's segment
-    const uint64_t b = __ballot(k >= hi || pred(k));
+    const uint64_t b = ballot64(k >= hi || pred(k));
     if (!b) return hi;
     const uint32_t i = (uint32_t)__ffsll((long long)b) - 1;
     lo = lo + i * step;
     hi = lo + step < hi ? lo + step : hi;
   }
   const uint32_t k = lo + lane;
-  const uint64_t b = __ballot(k < hi && pred(k));
+  const uint64_t b = ballot64(k < hi && pred(k));
   return b ? lo + (uint32_t)__ffsll((long long)b) - 1 : hi;
 }
 
@@ -706,35 +711,6 @@ __device__ __forceinline__ int64_t uniform_i64(int64_t x) {
   const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x);
   const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
   return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-// Monotone 16-bit code of a non-negative quantity: exact below 1024, then a
-// 9-bit mantissa per binade (relative step <= 2^-9).  codes are consecutive
-// in value order, so floor/ceil differ by at most one.
-__device__ __forceinline__ uint32_t qcode_floor(int64_t v) {
-  if (v <= 0) return 0;
-  const uint64_t x = (uint64_t)v;
-  const uint32_t b = 64u - (uint32_t)__clzll((long long)x);
-  if (b <= 10) return (uint32_t)x;
-  const uint32_t s = b - 10;
-  return 1024u + (s - 1) * 512u + (uint32_t)((x >> s) - 512u);
-}
-__device__ __forceinline__ uint32_t qcode_ceil(int64_t v) {
-  if (v <= 0) return 0;
-  const uint64_t x = (uint64_t)v;
-  const uint32_t b = 64u - (uint32_t)__clzll((long long)x);
-  if (b <= 10) return (uint32_t)x;
-  const uint32_t s = b - 10;
-  const uint32_t c = 1024u + (s - 1) * 512u + (uint32_t)((x >> s) - 512u);
-  return c + ((x & ((1ull << s) - 1)) ? 1u : 0u);
-}
-
-// the value a code stands for: qcode_floor(v) <= v's code <= qcode_ceil(v)
-// and qcode_value(qcode_floor(v)) <= v <= qcode_value(qcode_ceil(v))
-__device__ __forceinline__ int64_t qcode_value(uint32_t c) {
-  if (c < 1024u) return (int64_t)c;
-  const uint32_t s = (c - 1024u) / 512u + 1u, m = (c - 1024u) % 512u + 512u;
-  return (int64_t)((uint64_t)m << s);
 }
 
 // LDS room of a NodeClaim: qcode_floor(thr[cursor] - tot) per resource (<= 4),

@@ -57,9 +57,8 @@ constexpr uint32_t WREG = 4;  // option words a scoring lane keeps in registers
 #define GS_RING 16
 #endif
 constexpr uint32_t RING = GS_RING;  // first-pass pod records staged ahead of the solver
-constexpr uint32_t RING_DW = 53; // VarRec (32 dwords) + requests (<= 16 dwords) + request codes (4 dwords) + qrun
+constexpr uint32_t RING_DW = 52; // VarRec (32 dwords) + requests (<= 16 dwords) + request codes (4 dwords)
 constexpr uint32_t RING_CODES = 48;  // lanes 48..51: floor codes lo/hi dword, ceil codes lo/hi dword
-constexpr uint32_t RING_QRUN = 52;   // lane 52: qrun (records from here on with this one's spec, <= 16)
 constexpr uint32_t WQ = 32;      // global-memory write requests in flight
 constexpr uint32_t WQ_DW = 16;
 enum : uint32_t { WQ_LOG = 1, WQ_FA = 2, WQ_STOP = 3, WQ_NFA = 4 };
@@ -123,6 +122,13 @@ __device__ __forceinline__ KArg karg() {
   return p;
 }
 #endif
+// a device-memory address as a pointer the compiler knows to be global (a
+// plain cast of an integer gives a generic pointer: flat loads and stores,
+// which also count on the LDS / scalar counter)
+template <class T>
+__device__ __forceinline__ T* global_ptr(uint64_t a) {
+  return (T*)(__attribute__((address_space(1))) T*)a;
+}
 // an opaque copy: readlanes of it are not merged with earlier ones
 __device__ __forceinline__ uint32_t fresh(uint32_t x) {
   asm volatile("" : "+v"(x));
@@ -219,14 +225,14 @@ __device__ __noinline__ KnownPart known_partition(U32* so, int n, int pivot, int
   const int step = (n - 1 + 63) / 64;
   const int q = skip_e(1 + (int)lane * step);
   const bool qv = 1 + (int)lane * step < n && q < n;
-  const uint64_t m1 = __ballot(qv && key(qv ? q : 0) >= p);
+  const uint64_t m1 = ballot64(qv && key(qv ? q : 0) >= p);
   int lo, hi;  // t is in [lo, hi]
   if (m1) {
     const int l = (int)ffs64(m1);
     lo = l == 0 ? 1 : (int)rlane((uint32_t)q, (uint32_t)(l - 1)) + 1;
     hi = (int)rlane((uint32_t)q, (uint32_t)l);
   } else {
-    const int lv = 63 - (int)__clzll((long long)__ballot(qv));
+    const int lv = 63 - (int)__clzll((long long)ballot64(qv));
     lo = (int)rlane((uint32_t)q, (uint32_t)lv) + 1;
     hi = n;
   }
@@ -234,7 +240,7 @@ __device__ __noinline__ KnownPart known_partition(U32* so, int n, int pivot, int
   for (int base = lo; base < hi; base += 64) {
     const int k = base + (int)lane;
     const bool ok = k < hi && k < n && !in_e(k);
-    const uint64_t m2 = __ballot(ok && key(ok ? k : 0) >= p);
+    const uint64_t m2 = ballot64(ok && key(ok ? k : 0) >= p);
     if (m2) {
       t = base + (int)ffs64(m2);
       break;
@@ -303,7 +309,7 @@ __device__ __noinline__ KnownPart known_partition(U32* so, int n, int pivot, int
       right = pos > mid && ke < p;
     }
   }
-  const uint64_t lm = __ballot(left), rm = __ballot(right);
+  const uint64_t lm = ballot64(left), rm = ballot64(right);
   const uint32_t s = (uint32_t)__popcll(lm);
   if (s) {
     // ranks (left ascending, right descending by position) and partners
@@ -367,7 +373,7 @@ struct WaveSort {
         in[u] = k < hi && pred(k);
       }
 #pragma unroll
-      for (int u = 0; u < RW; u++) c += (uint32_t)__popcll(__ballot(in[u]));
+      for (int u = 0; u < RW; u++) c += (uint32_t)__popcll(ballot64(in[u]));
     }
     return c;
   }
@@ -386,7 +392,7 @@ struct WaveSort {
 #pragma unroll
       for (int u = 0; u < RW; u++) {
         const int idx = base + u * 64 + (int)lane;
-        const uint64_t m = __ballot(in[u]);
+        const uint64_t m = ballot64(in[u]);
         if (in[u]) out[total + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(desc ? hi - 1 - idx : lo + idx);
         total += (uint32_t)__popcll(m);
       }
@@ -432,7 +438,7 @@ struct WaveSort {
         const bool valid = k < hi;
         const bool in = valid && (LE ? kk[u] <= p : kk[u] < p);
         const bool out = valid && !in;
-        const uint64_t bi = __ballot(in);
+        const uint64_t bi = ballot64(in);
         c += (uint32_t)__popcll(bi);
         mine = lane == (uint32_t)((base - lo) / 64 + u) ? bi : mine;
         const uint32_t nk = 0xFFFFu - kk[u];
@@ -607,7 +613,7 @@ struct WaveSort {
       for (int u = 0; u < RW; u++) hit[u] = base + u * 64 + (int)lane < b && kc[u] < kp[u];
 #pragma unroll
       for (int u = 0; u < RW; u++) {
-        const uint64_t m = __ballot(hit[u]);
+        const uint64_t m = ballot64(hit[u]);
         if (m) return base + u * 64 + (int)ffs64(m);
       }
     }
@@ -628,7 +634,7 @@ struct WaveSort {
         int q = -1;
         for (int top = i - 2; top >= 0; top -= 64) {
           const int k = top - (int)lane;
-          const uint64_t m = __ballot(k >= 0 && key(k) <= x);
+          const uint64_t m = ballot64(k >= 0 && key(k) <= x);
           if (m) {
             q = top - (int)ffs64(m);  // lowest lane = highest position
             break;
@@ -641,7 +647,7 @@ struct WaveSort {
         int q = b;
         for (int base = i + 1; base < b; base += 64) {
           const int k = base + (int)lane;
-          const uint64_t m = __ballot(k < b && key(k) >= y);
+          const uint64_t m = ballot64(k < b && key(k) >= y);
           if (m) {
             q = base + (int)ffs64(m);
             break;
@@ -1019,7 +1025,6 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             if (lane < VR_DW) val[i] = qv_dw[k * VR_DW + lane];
             else if (lane < 32 + 2 * R) val[i] = qr_dw[k * 2 * R + (lane - 32)];
             else if (lane >= RING_CODES && lane < RING_CODES + 4) val[i] = d.qcodes[k * 4 + (lane - RING_CODES)];
-            else if (lane == RING_QRUN) val[i] = d.qrun[k];
           }
         }
 #pragma unroll
@@ -1107,6 +1112,46 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
     }
   };
 
+  // Hot kernel arguments.  The pointers every placed pod uses (the add log,
+  // the claim records and option words, the K1 rows, the threshold sets, the
+  // working nodes) and the sizes its exact check reads sit in the lanes of one
+  // register pair, staged once here; a use site reads its lane (HP, HU: a
+  // readlane, no memory counter) where a scalar load from the kernel
+  // arguments would stall the wave on lgkmcnt(0) -- which also drains the
+  // ring prefetch of the next pod's record.  The cold paths (a new NodeClaim,
+  // a generic sort, relax / push) still read the arguments through karg().
+  enum : uint32_t { HP_LOG = 0, HP_CREC, HP_COPTS, HP_ROWS, HP_THRSET, HP_NODES, HP_N,
+                    HU_Z = 8, HU_C, HU_RQ, HU_NN };
+  uint32_t hp_lo = 0, hp_hi = 0;
+  {
+    const uint64_t hp[HP_N] = {(uint64_t)d.log,  (uint64_t)d.c_rec,   (uint64_t)d.c_opts,
+                               (uint64_t)d.rows, (uint64_t)d.thr_set, (uint64_t)d.nodes};
+#pragma unroll
+    for (uint32_t k = 0; k < HP_N; k++)
+      if (lane == k) {
+        hp_lo = (uint32_t)hp[k];
+        hp_hi = (uint32_t)(hp[k] >> 32);
+      }
+    hp_lo = lane == HU_Z ? d.Z : lane == HU_C ? d.C : lane == HU_RQ ? d.RQ : lane == HU_NN ? d.NN : hp_lo;
+  }
+  auto HP = [&](uint32_t k) -> uint64_t { return (uint64_t)rlane(hp_lo, k) | ((uint64_t)rlane(hp_hi, k) << 32); };
+  auto HU = [&](uint32_t k) -> uint32_t { return rlane(hp_lo, k); };
+  struct HotRQ {  // pack_slack's view of the problem: the prefilter's resource count
+    uint32_t RQ;
+  };
+  struct HotKD {  // the exact check's and the winner Add's view of the kernel arguments
+    ClaimRec* c_rec;
+    uint64_t* c_opts;
+    const uint64_t* rows;
+    const uint64_t* thr_set;
+    uint32_t Z, C, RQ;
+  };
+  auto hot = [&]() -> HotKD {
+    return HotKD{global_ptr<ClaimRec>(HP(HP_CREC)),      global_ptr<uint64_t>(HP(HP_COPTS)),
+                 global_ptr<const uint64_t>(HP(HP_ROWS)), global_ptr<const uint64_t>(HP(HP_THRSET)),
+                 HU(HU_Z), HU(HU_C), HU(HU_RQ)};
+  };
+
   // Solver-side global writes: the add log entry (lane 0) and, for a
   // requests-only Add, the no-return atomic adds of the requests (lanes
   // r < min(R, 4)).  They are fire-and-forget: the next exact check's loads
@@ -1117,11 +1162,10 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
       post(type, idx, pod, var, tgt, rqd_);
       return;
     }
-    const auto& KD = *karg();
-    if (lane == 0) KD.log[idx] = LogRec{pod, var, type == WQ_NFA ? tgt | 0x80000000u : tgt, 0};
+    if (lane == 0) global_ptr<LogRec>(HP(HP_LOG))[idx] = LogRec{pod, var, type == WQ_NFA ? tgt | 0x80000000u : tgt, 0};
     if ((type == WQ_FA || type == WQ_NFA) && lane < R && lane < 4 && rql != 0) {
-      unsigned long long* a = type == WQ_FA ? (unsigned long long*)&KD.c_rec[tgt].tot_lo[lane]
-                                            : (unsigned long long*)&KD.nodes[tgt].req[lane];
+      unsigned long long* a = type == WQ_FA ? (unsigned long long*)&global_ptr<ClaimRec>(HP(HP_CREC))[tgt].tot_lo[lane]
+                                            : (unsigned long long*)&global_ptr<NodeRec>(HP(HP_NODES))[tgt].req[lane];
       atomicAdd(a, (unsigned long long)rql);
     }
   };
@@ -1212,8 +1256,12 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
     if (!TOPO && !WIDE && run_prev && !wrapped && modkind == MOD_INC && M >= 50 &&
         (d.NN == 0 || (nhint_ok && nhint >= d.NN))) {
       run_prev = false;
+      // (a vote over a conjunction goes through a 0/1 value per lane and a
+      // second compare; the votes of its comparisons, ANDed as masks, do not:
+      // every lane of the solver wave is active at each of these sites)
       auto same_spec = [&](uint32_t x) {
-        return __ballot(lane >= 1 && lane < RING_QRUN && lane != VR_DW - 1 && x != run_rec) == 0;
+        constexpr uint64_t spec_lanes = ((1ull << RING_DW) - 1ull) & ~1ull & ~(1ull << (VR_DW - 1));
+        return (ballot64(x != run_rec) & spec_lanes) == 0;
       };
       if (__builtin_amdgcn_readfirstlane(pf_seq) == qhead + 1 && same_spec(pf_x)) {
         // the run's spec: tolerated templates, request codes and requests
@@ -1249,6 +1297,11 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
         load_window();
         uint32_t lf = 0;  // lane of the claim the last Add raised
         bool dirty = false;
+        // the run's share of the candidate, fast-accept, CanAdd and pod
+        // counters: uniform, summed in scalars and added to the counter lanes
+        // once, where the run ends (whatever ends it)
+        uint64_t rc_cand = 0, rc_alg = 0;
+        uint32_t rc_fa = 0, rc_pods = 0;
         CTR(C_RENTER, 1);
         CAT(0);
 #ifdef GS_RUN_TL
@@ -1258,7 +1311,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
           // sort.Slice: the raised claim moves to the end of its run of equal keys
           const uint32_t x = rlane(ow, lf) & 0xFFFFu;
           const bool ptouch = pivot_touched(MOD_INC, modpos, M);
-          const uint64_t b = ptouch ? 0ull : __ballot(lane > lf && (ow & 0xFFFFu) >= x);
+          const uint64_t b = ptouch ? 0ull : ballot64((ow & 0xFFFFu) >= x) & (~1ull << lf);  // lanes > lf
           const uint32_t eo = b ? ffs64(b) : 64u;
           if (!b) {
             // a pivot sample touched, or the raised claim's run of equal keys
@@ -1310,8 +1363,8 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
           // the scan from the infeasible-prefix bound (the last Add's
           // position): the first candidate must be a fast accept
           const uint32_t lo = modpos - base;
-          const bool lp = (lane >= lo) & valid & (wtok != 0) & swar_ge(wsl, r_rqq);
-          const uint64_t lpb = __ballot(lp), fab = __ballot(lp & swar_ge(wrm, r_rqc));
+          const uint64_t lpb = ballot64(lane >= lo) & ballot64(wpos < M) & ballot64(wtok != 0) & ballot64(swar_ge(wsl, r_rqq));
+          const uint64_t fab = lpb & ballot64(swar_ge(wrm, r_rqc));
           if (!lpb) {
             CTR(C_RX_SCAN, 1);
             break;
@@ -1346,7 +1399,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             }
             const uint32_t mfl = fab ? ffs64(fab) : 64u;
             const uint64_t ex = lpb & ~fab & (mfl == 64 ? ~0ull : ((1ull << mfl) - 1ull));
-            const auto& KD = *karg();
+            const HotKD KD = hot();
             const uint32_t pvx = rlane(pf_x, VR_DW - 1);  // the next pod's variant (its K1 rows)
             bool feas = false;
             if ((ex >> lane) & 1) {
@@ -1427,7 +1480,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             }
             CTR(C_FULL, __popcll(ex));
             CTR(C_RX_XC, 1);
-            const uint64_t fm = __ballot(feas);
+            const uint64_t fm = ballot64(feas);
             if (fm) {
               fl = ffs64(fm);
               xwin = true;
@@ -1458,7 +1511,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             // NodeClaim.Add after the exact check, by the winning lane (as
             // the general path's): options, requests, cursors, the exact
             // slack / room codes, requirements; the window takes the codes
-            const auto& KD = *karg();
+            const HotKD KD = hot();
             const uint32_t vctb = rlane(run_rec, 3);
             if (lane == fl) {
               const uint32_t j = ow >> 16;
@@ -1476,7 +1529,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
                 cr->tot(r) = nt[r];
                 cr->thr(r) = (uint16_t)cu[r];
               }
-              wsl = pack_slack(d, x_ma, nt);
+              wsl = pack_slack(HotRQ{KD.RQ}, x_ma, nt);
               wrm = pack_room(thr, s_thoff, cu, nt, KD.RQ);
               s_slk[j] = wsl;
               s_rm[j] = wrm;
@@ -1490,10 +1543,9 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             wsyncT<CH>();
             emit(WQ_LOG, nlog, pp, pv, e >> 16, 0, 0);
             nlog++;
-            CTR(C_CAND, M - modpos < 64 ? M - modpos : 64);
-            CTR(C_ALG, f + 1);
-            CTR(C_NPRE, d.NN);  // every existing node was tried first
-            CTR(C_RPODS, 1);
+            rc_cand += M - modpos < 64 ? M - modpos : 64;
+            rc_alg += f + 1;
+            rc_pods++;
 #ifdef GS_CAT_TL
             cat_n += lane == 0 ? 1ull : 0ull;
 #endif
@@ -1508,12 +1560,11 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
           // resource r, packed across lanes 0..3 as in the general path)
           const uint64_t rm = ((uint64_t)rlane((uint32_t)(wrm >> 32), fl) << 32) | rlane((uint32_t)wrm, fl);
           const uint64_t sl = ((uint64_t)rlane((uint32_t)(wsl >> 32), fl) << 32) | rlane((uint32_t)wsl, fl);
-          uint32_t c_rm = 0, c_sl = 0;
-          if (lane < d.RQ) {
-            const uint32_t sh = 16 * lane;
-            c_rm = qcode_floor(qcode_value((uint32_t)(rm >> sh) & 0xFFFFu) - r_rq);
-            c_sl = qcode_ceil(qcode_value((uint32_t)(sl >> sh) & 0xFFFFu) - r_rq);
-          }
+          // (selects, not an early return per lane; lanes >= RQ keep 0)
+          const uint32_t sh = 16 * (lane & 3u);
+          const bool rl = lane < HU(HU_RQ);
+          const uint32_t c_rm = rl ? qcode_floor(qcode_value((uint32_t)(rm >> sh) & 0xFFFFu) - r_rq) : 0u;
+          const uint32_t c_sl = rl ? qcode_ceil(qcode_value((uint32_t)(sl >> sh) & 0xFFFFu) - r_rq) : 0u;
           uint32_t prm = (lane & 1u) ? c_rm << 16 : c_rm, psl = (lane & 1u) ? c_sl << 16 : c_sl;
           prm |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)prm, 0xB1, 0xF, 0xF, false);  // quad_perm [1,0,3,2]
           psl |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)psl, 0xB1, 0xF, 0xF, false);
@@ -1530,11 +1581,10 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
           const uint32_t f = base + fl;
           emit(WQ_FA, nlog, pp, pv, e >> 16, run_rec, r_rq);  // the requests into the claim totals, and the log
           nlog++;
-          CTR(C_CAND, M - modpos < 64 ? M - modpos : 64);
-          CTR(C_FA, 1);
-          CTR(C_ALG, f + 1);
-          CTR(C_NPRE, d.NN);  // every existing node was tried first
-          CTR(C_RPODS, 1);
+          rc_cand += M - modpos < 64 ? M - modpos : 64;
+          rc_fa++;
+          rc_alg += f + 1;
+          rc_pods++;
 #ifdef GS_CAT_TL
           cat_n += lane == 0 ? 1ull : 0ull;
 #endif
@@ -1543,6 +1593,13 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
           modpos = f;
           lf = fl;
         }
+        // (C_NPRE: every existing node was tried before each of the run's pods)
+        ctr += lane == C_CAND    ? rc_cand
+               : lane == C_FA    ? (uint64_t)rc_fa
+               : lane == C_ALG   ? rc_alg
+               : lane == C_NPRE  ? (uint64_t)rc_pods * d.NN
+               : lane == C_RPODS ? (uint64_t)rc_pods
+                                 : 0ull;
         if (dirty) {
           // the window back to LDS: positions, and the codes of its claims
           wsyncT<CH>();
@@ -1656,7 +1713,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
       if (lane < RR) rq_lane = (int64_t)(((uint64_t)hi << 32) | lo);
     }
     // resources 4.. requested at all (the LDS codes cover resources 0..3)
-    const bool rq_hi = RR > 4 && __ballot(lane >= 4 && lane < RR && rq_lane != 0) != 0;
+    const bool rq_hi = RR > 4 && ballot64(lane >= 4 && lane < RR && rq_lane != 0) != 0;
     if (!from_ring) {
       // a wrapped pop read its record itself: the request codes too
       GS_RQ_AT(RQ);
@@ -1682,6 +1739,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
     // ----------------- existing nodes in order: first ExistingNode.CanAdd wins
     if (d.NN) {
       const auto& KD = *karg();
+      const uint32_t nn = HU(HU_NN);  // the scan's bound from its lane: no scalar load per pod
       const uint32_t vx = fresh(vrd);
       auto VX = [&](uint32_t i) -> uint32_t { return rlane(vx, i); };
       auto VX64 = [&](uint32_t i) -> uint64_t { return (uint64_t)VX(i) | ((uint64_t)VX(i + 1) << 32); };
@@ -1709,28 +1767,28 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
       const uint64_t nrqq = rqq_p, nrqc = rqc_p;
       uint32_t nlo = 0;
       if (nhint_ok && (vtol & ~nhint_tol) == 0) {
-        const bool ge = lane >= R || rq_lane >= hint_nrq;
-        if (__ballot(!ge) == 0) nlo = nhint;
+        // every lane r < R: this pod's request r >= the hint's
+        if ((ballot64(rq_lane < hint_nrq) & ((1ull << RR) - 1ull)) == 0) nlo = nhint;
       }
       uint32_t fn = INF;
       bool nfa_win = false;
       GS_RQ_AT(RQ);  // in uniform control flow: the copy must hold every lane
-      for (uint32_t base = nlo & ~63u; base < KD.NN; base += 64) {
+      for (uint32_t base = nlo & ~63u; base < nn; base += 64) {
         const uint32_t n = base + lane;
-        const bool in = (n < KD.NN) & (n >= nlo);
+        const bool in = (n < nn) & (n >= nlo);
         const uint32_t nc = in ? n : 0u;
         const uint64_t nsl = s_nslk[nc], nrm = s_nrm[nc];
         const uint32_t nfl = s_nflag[nc];
         const bool lp = in & swar_ge(nsl, nrqq);
         const bool fa = lp & nplain & (bool)(nfl & 1u) & swar_ge(nrm, nrqc);
-        const uint64_t lpb = __ballot(lp);
-        CTR(C_NEV, KD.NN - base < 64 ? KD.NN - base : 64);
+        const uint64_t lpb = ballot64(lp);
+        CTR(C_NEV, nn - base < 64 ? nn - base : 64);
         if (!lpb) continue;
-        const uint64_t fab = __ballot(fa);
+        const uint64_t fab = ballot64(fa);
         const uint32_t mfl = fab ? ffs64(fab) : 64u;
         const bool need = lp & !fa & (lane < mfl);
         bool feas = fa;
-        if (__ballot(need)) {
+        if (ballot64(need)) {
           if (need) {
             const NodeRec& nr = KD.nodes[n];
             const FK* nfk = KD.n_fk + (size_t)n * F;
@@ -1761,17 +1819,17 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             }
           }
         }
-        const uint64_t b = __ballot(feas);
+        const uint64_t b = ballot64(feas);
         if (b) {
           fn = base + ffs64(b);
           nfa_win = ((fab >> ffs64(b)) & 1) != 0;
           break;
         }
       }
-      CTR(C_NPRE, fn != INF ? fn + 1 : KD.NN);
+      CTR(C_NPRE, fn != INF ? fn + 1 : nn);
       if (nplain) {
         // [nlo, fn) (or all) cannot take these requests; nodes only fill up
-        nhint = fn != INF ? fn : KD.NN;
+        nhint = fn != INF ? fn : nn;
         nhint_ok = true;
         nhint_tol = vtol;
         hint_nrq = rq_lane;
@@ -1782,7 +1840,8 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
         // the requests to the node (an exact check drains the channel first)
         const uint64_t sl = s_nslk[fn], rm = s_nrm[fn];
         uint32_t c_sl = 0, c_rm = 0;
-        if (lane < KD.RQ) {
+        const uint32_t hrq = HU(HU_RQ);
+        if (lane < hrq) {
           const uint32_t sh = 16 * lane;
           c_sl = qcode_ceil(qcode_value((uint32_t)(sl >> sh) & 0xFFFFu) - rq_lane);
           c_rm = qcode_floor(qcode_value((uint32_t)(rm >> sh) & 0xFFFFu) - rq_lane);
@@ -1790,7 +1849,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
         uint64_t sl2 = 0, rm2 = 0;
 #pragma unroll
         for (uint32_t r = 0; r < 4; r++)
-          if (r < KD.RQ) {
+          if (r < hrq) {
             sl2 |= (uint64_t)rlane(c_sl, r) << (16 * r);
             rm2 |= (uint64_t)rlane(c_rm, r) << (16 * r);
           }
@@ -1838,7 +1897,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             sl2 |= (uint64_t)rlane(c_sl, r) << (16 * r);
             rm2 |= (uint64_t)rlane(c_rm, r) << (16 * r);
           }
-          const bool anyover = __ballot(over) != 0;
+          const bool anyover = ballot64(over) != 0;
           if (lane == 0) {
             s_nslk[fn] = sl2;
             s_nrm[fn] = rm2;
@@ -1883,7 +1942,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
       const uint32_t k = modpos + lane;
       const uint32_t w = k < M ? (uint32_t)acc.so[k] : 0xFFFFu;
       const uint32_t w0 = rlane(w, 0), x = w0 & 0xFFFFu;
-      const uint64_t b = __ballot(lane >= 1 && (w & 0xFFFFu) >= x);
+      const uint64_t b = ballot64((w & 0xFFFFu) >= x) & ~1ull;  // lanes >= 1
       if (b) {
         const uint32_t eo = ffs64(b);  // e = modpos + eo
         if (eo > 1) {
@@ -1993,8 +2052,8 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
     bool ovf = false;  // the winner lane's u16 pod count overflowed
     uint32_t lo_bound = 0;
     if (hint_ok && (vtolt & ~hint_tolt) == 0) {
-      const bool ge = lane >= 4 || lane >= R || rq_lane >= hint_rq;
-      if (__ballot(!ge) == 0) lo_bound = hint;
+      // every lane r < min(R, 4): this pod's request r >= the hint's
+      if ((ballot64(rq_lane < hint_rq) & ((1ull << (RR < 4 ? RR : 4u)) - 1ull)) == 0) lo_bound = hint;
     }
     uint32_t scan_from = lo_bound;  // chunks start at the bound (no dead lanes below it)
     for (;;) {
@@ -2033,8 +2092,12 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             lp = lp && c <= (int64_t)(int32_t)rlane(og_skew, k);
           }
         }
-        const bool fa = lp & (simple | hostfa) & swar_ge(rmv, rqc_p);
-        const uint64_t fab = __ballot(fa), exb = __ballot(lp & !fa);
+        // (fa = lp & (simple | hostfa) & room test, exb = lp & !fa, as masks)
+        const uint64_t lpb = TOPO ? ballot64(lp)
+                                  : ballot64(pos >= lo_bound) & ballot64(pos < M) & ballot64(((vtolt >> tt) & 1) != 0) &
+                                        ballot64(swar_ge(sq, rqq_p));
+        const uint64_t fab = (simple | hostfa) ? lpb & ballot64(swar_ge(rmv, rqc_p)) : 0ull;
+        const uint64_t exb = lpb & ~fab;
         const uint32_t mfl = fab ? ffs64(fab) : 64u;
         const uint64_t ex = exb & (mfl == 64 ? ~0ull : ((1ull << mfl) - 1ull));
         const uint32_t cnt = (uint32_t)__popcll(ex);
@@ -2060,7 +2123,8 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
       wsyncT<CH>();
       TLW(5);  // phase A: LDS prefilter
       if (nex) {
-        const auto& KD = *karg();
+        const auto& KD = *karg();  // (the rare fields: free keys, topology, minValues)
+        const HotKD HK = hot();
         const uint32_t vx = fresh(vrd);
         auto VX = [&](uint32_t i) -> uint32_t { return rlane(vx, i); };
         auto VX64 = [&](uint32_t i) -> uint64_t { return (uint64_t)VX(i) | ((uint64_t)VX(i + 1) << 32); };
@@ -2100,7 +2164,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
       uint64_t nx[WREG] = {0, 0, 0, 0};
       uint64_t G = 0, Gt = 0;
       if (cx < nex) {
-        const ClaimRec* cr = KD.c_rec + j;
+        const ClaimRec* cr = HK.c_rec + j;
         uint32_t cur[RR];
 #pragma unroll
         for (uint32_t r = 0; r < RR; r++) maxa_pre[r] = cr->maxa[r];
@@ -2118,8 +2182,8 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             cur[r] = r < 4 ? cl[r] : cr->thr_hi[r - 4];
           }
         }
-        const uint64_t* row = KD.rows + ((size_t)v * T + t) * OW;
-        const uint64_t* opts = KD.c_opts + (size_t)j * OW;
+        const uint64_t* row = HK.rows + ((size_t)v * T + t) * OW;
+        const uint64_t* opts = HK.c_opts + (size_t)j * OW;
         if (!WIDE) {
           const uint4* oq = (const uint4*)opts;
           const uint4* rq4 = (const uint4*)row;
@@ -2149,8 +2213,8 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
           }
         }
         if (pre) {
-          G = grid_of(zm & vzm, cm & vcm, KD.Z, KD.C);
-          Gt = grid_of(s_tzm[t] & vzm, s_tcm[t] & vcm, KD.Z, KD.C);
+          G = grid_of(zm & vzm, cm & vcm, HK.Z, HK.C);
+          Gt = grid_of(s_tzm[t] & vzm, s_tcm[t] & vcm, HK.Z, HK.C);
           uint32_t mm[RR];
 #pragma unroll
           for (uint32_t r = 0; r < RR; r++) {
@@ -2170,7 +2234,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
 #pragma unroll
             for (uint32_t r = 0; r < RR; r++) {
               if (mm[r] != cur[r]) {
-                const uint4* tq = (const uint4*)(KD.thr_set + (size_t)mrow[r] * OW);
+                const uint4* tq = (const uint4*)(HK.thr_set + (size_t)mrow[r] * OW);
                 const uint4 t0 = tq[0], t1 = tq[1];
                 nx[0] &= ((uint64_t)t0.y << 32) | t0.x;
                 nx[1] &= ((uint64_t)t0.w << 32) | t0.z;
@@ -2212,7 +2276,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
 #pragma unroll
                   for (uint32_t r = 0; r < RR; r++) {
                     if (mm[r] == cur[r]) continue;
-                    const uint4* tq = (const uint4*)(KD.thr_set + (size_t)mrow[r] * OW + wc);
+                    const uint4* tq = (const uint4*)(HK.thr_set + (size_t)mrow[r] * OW + wc);
                     tt[c][r][0] = tq[0];
                     tt[c][r][1] = tq[1];
                   }
@@ -2248,7 +2312,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             }
           }
           // the candidate's lanes (all active: pre is per candidate)
-          const uint64_t gb = __ballot(accw != 0);
+          const uint64_t gb = ballot64(accw != 0);
           feas = ((gb >> (lane & ~((1u << lg) - 1u))) & ((1ull << (1u << lg)) - 1ull)) != 0;
           if (TOPO && feas && KD.tmpl[t].mv_mask) {
             // minValues over the NodeClaim's options after Add (per lane)
@@ -2256,7 +2320,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
               if (!WIDE) return w == 0 ? nx[0] : w == 1 ? nx[1] : w == 2 ? nx[2] : nx[3];
               uint64_t x = opts[w] & row[w];
 #pragma unroll
-              for (uint32_t r = 0; r < RR; r++) x &= KD.thr_set[(size_t)mrow[r] * OW + w];
+              for (uint32_t r = 0; r < RR; r++) x &= HK.thr_set[(size_t)mrow[r] * OW + w];
               if (G != Gt) {
                 uint64_t off = 0;
                 for (uint64_t gm = G; gm; gm &= gm - 1) off |= slot[(size_t)ffs64(gm) * W + w];
@@ -2267,7 +2331,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
           }
         }
       }
-        const uint64_t fm = __ballot(feas);
+        const uint64_t fm = ballot64(feas);
         TLW(6);  // phase B: exact checks
         if (fm) {
           const uint32_t wl = ffs64(fm);
@@ -2285,12 +2349,12 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
           for (uint32_t r = 0; r < RR; r++) mw[r] = rlane(mrow[r], wl);
           const uint64_t Gw = ((uint64_t)rlane((uint32_t)(G >> 32), wl) << 32) | rlane((uint32_t)G, wl);
           const uint64_t Gtw = ((uint64_t)rlane((uint32_t)(Gt >> 32), wl) << 32) | rlane((uint32_t)Gt, wl);
-          uint64_t* wopts = KD.c_opts + (size_t)jw * OW;
-          const uint64_t* row = KD.rows + ((size_t)v * T + tw) * OW;
+          uint64_t* wopts = HK.c_opts + (size_t)jw * OW;
+          const uint64_t* row = HK.rows + ((size_t)v * T + tw) * OW;
           for (uint32_t w = lane; w < W; w += 64) {
             uint64_t x = wopts[w] & row[w];
   #pragma unroll
-            for (uint32_t r = 0; r < RR; r++) x &= KD.thr_set[(size_t)mw[r] * OW + w];
+            for (uint32_t r = 0; r < RR; r++) x &= HK.thr_set[(size_t)mw[r] * OW + w];
             if (Gw != Gtw) {
               uint64_t off = 0;
               for (uint64_t gm = Gw; gm; gm &= gm - 1) off |= slot[(size_t)ffs64(gm) * W + w];
@@ -2302,8 +2366,8 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
         if (lane == wl) {
           // NodeClaim.Add by the winning lane: options (wide rows: above),
           // requests, requirements
-          ClaimRec* cr = KD.c_rec + j;
-          uint64_t* opts = KD.c_opts + (size_t)j * OW;
+          ClaimRec* cr = HK.c_rec + j;
+          uint64_t* opts = HK.c_opts + (size_t)j * OW;
           if (!WIDE) {
   #pragma unroll
             for (uint32_t w = 0; w < WREG; w++)
@@ -2319,8 +2383,8 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             cr->tot(r) = nt[r];
             cr->thr(r) = (uint16_t)cu[r];
           }
-          s_slk[j] = pack_slack(d, ma, nt);  // exact re-quantization: no drift
-          s_rm[j] = pack_room(thr, s_thoff, cu, nt, KD.RQ);
+          s_slk[j] = pack_slack(HotRQ{HK.RQ}, ma, nt);  // exact re-quantization: no drift
+          s_rm[j] = pack_room(thr, s_thoff, cu, nt, HK.RQ);
           cr->zm = zm & vzm;  // zm (dom_ct: cm) carries the topology narrowing
           cr->cm = cm & vcm;
           cr->ctb &= vctb;
@@ -2373,12 +2437,11 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
           const uint64_t rm = ((uint64_t)rlane((uint32_t)(fa_rv >> 32), fl) << 32) | rlane((uint32_t)fa_rv, fl);
           const uint64_t sl = ((uint64_t)rlane((uint32_t)(fa_sq >> 32), fl) << 32) | rlane((uint32_t)fa_sq, fl);
           const uint32_t e = rlane(fa_ev, fl);
-          uint32_t c_rm = 0, c_sl = 0;
-          if (lane < d.RQ) {
-            const uint32_t sh = 16 * lane;
-            c_rm = qcode_floor(qcode_value((uint32_t)(rm >> sh) & 0xFFFFu) - rq_lane);
-            c_sl = qcode_ceil(qcode_value((uint32_t)(sl >> sh) & 0xFFFFu) - rq_lane);
-          }
+          // (selects, not an early return per lane; lanes >= RQ keep 0)
+          const uint32_t sh = 16 * (lane & 3u);
+          const bool rl = lane < HU(HU_RQ);
+          const uint32_t c_rm = rl ? qcode_floor(qcode_value((uint32_t)(rm >> sh) & 0xFFFFu) - rq_lane) : 0u;
+          const uint32_t c_sl = rl ? qcode_ceil(qcode_value((uint32_t)(sl >> sh) & 0xFFFFu) - rq_lane) : 0u;
           uint32_t prm = (lane & 1u) ? c_rm << 16 : c_rm, psl = (lane & 1u) ? c_sl << 16 : c_sl;
           prm |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)prm, 0xB1, 0xF, 0xF, false);  // quad_perm [1,0,3,2]
           psl |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)psl, 0xB1, 0xF, 0xF, false);
@@ -2407,7 +2470,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
       if (resume == INF) break;
       scan_from = resume;
     }
-    if (__ballot(ovf)) status = 3;
+    if (ballot64(ovf)) status = 3;
     CTR(C_ALG, f != INF ? f + 1 : M);  // the reference's NodeClaim.CanAdd calls
     TLW(3);  // scan + Add
 #ifdef GS_FFD_TL
@@ -2426,7 +2489,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
       modpos = f;
       nlog++;
       // the next pod may repeat this one's spec (runs, above)
-      run_prev = !TOPO && !WIDE && from_ring && simple && !__ballot(ovf);
+      run_prev = !TOPO && !WIDE && from_ring && simple && !ballot64(ovf);
       CAT(simple ? 1 : 3);
       run_rec = vrd;
       continue;
@@ -2477,7 +2540,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
       bool anyl = false;
       if (KD.fk_ok[(size_t)v * T + t])
         for (uint32_t w = lane; w < W; w += 64) anyl = anyl || rowx(w) != 0;
-      if (!__ballot(anyl)) continue;
+      if (!ballot64(anyl)) continue;
       if (tr.has_limits) {
         // <U> filterByRemainingResources on the template's options
         bool hit = false;
@@ -2488,7 +2551,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             if ((tr.limit_rmask >> r) & 1) ok = ok && KD.it_cap[(size_t)r * KD.N + i] <= KD.t_rem[(size_t)t * R + r];
           hit = hit || ok;
         }
-        if (!__ballot(hit)) continue;
+        if (!ballot64(hit)) continue;
       }
       // threshold cursors of the fresh claim: lane r < R
       int64_t tot_l = 0;
