@@ -559,6 +559,50 @@ gs_status gs_batch_run(gs_ctx* ctx);
  * slot i's status when it was refused; valid until the next batch prepare, the
  * next fetch of the same slot, or gs_destroy */
 gs_status gs_batch_fetch(gs_ctx* ctx, uint32_t i, gs_result* out);
+/* Every slot's scheduling.Results in one device pass: out[i] and status[i] for
+ * each of the batch's n slots (n as given to the last gs_batch_prepare).
+ * status[i] is what gs_batch_fetch(ctx, i, ...) would return on the same run:
+ * the slot's prepare status when it was refused, GS_OK when its fetch
+ * succeeds, or the slot's own failure (GS_E_CAPACITY when the Solve ran out of
+ * NodeClaim slots or a NodeClaim's 16-bit pod count; GS_E_HIP for an internal
+ * or unknown kernel status or for records that fail validation), which leaves
+ * the other slots alone (message: gs_batch_error).  For a slot with GS_OK,
+ * out[i] equals field by field what gs_batch_fetch yields for slot i on the
+ * same run: NodeClaims, node pods, error pods, requirement text, requests and
+ * instance-type lists, and checks, pops, cand_evals, cand_full, claim_prefix,
+ * node_prefix, sorts_fast, sorts_generic, the t_ffd_*_ms phase fields, words,
+ * n_templates and n_variants.  Only t_fetch_ms (the whole call's wall clock,
+ * the same value in every slot) and t_total_ms (which contains it) differ.
+ * out[i] points into slot i's own result storage, so all n results are valid
+ * at once, each until the next batch prepare, the next fetch of that slot (per
+ * slot or all) or gs_destroy; out[i] is zeroed where status[i] is not GS_OK.
+ * Cost: the slots the batched launches solved are gathered by two kernel
+ * launches (sizes with a prefix sum in slot order, then the copy) into one
+ * staging buffer: a 128-byte record per slot, then each slot's add log
+ * (16 B per placed pod), NodeClaim headers and OrderByPrice rows (192 + 240 +
+ * 4 B per NodeClaim) and unplaced pods (4 B each, the queue ring unrolled on
+ * the device).  It comes back in one transfer and one synchronisation; the
+ * transfer carries as much as the batch's previous gs_batch_fetch_all found,
+ * and when the run left more, as in the first call after a prepare, a second
+ * transfer brings the rest (and, when the staging buffer itself was too small,
+ * a second pair of launches first).  The number of device operations does not
+ * depend on n.  Each gathered slot is checked against the transferred size and
+ * its own bounds and decoded on up to 16 host threads.  A slot the run solved
+ * alone (gs_batch_stats.n_fallback) is fetched as gs_batch_fetch does.  For a
+ * single slot gs_batch_fetch is the cheaper call.
+ * The stats reuse the struct gs_batch_fetch_stats declared below: n_decided counts the
+ * accepted slots decoded from the gathered records, n_per_slot the fallback
+ * slots, n_launches the gather's kernel launches, n_copies / bytes every
+ * device-to-host transfer, the per-slot path's included.
+ * GS_E_INVALID: NULL ctx, NULL out or status with n > 0, no prepared batch, or
+ * the batch has not run.  n = 0 returns GS_OK with no device operation.
+ * GS_E_HIP: the gather itself failed.  gs_batch_fetch, gs_batch_run and the
+ * context's own prepared problem behave as before, in any order with this
+ * call. */
+struct gs_batch_fetch_stats;
+gs_status gs_batch_fetch_all(gs_ctx* ctx, gs_result* out /*[n]*/, gs_status* status /*[n]*/);
+/* counters and times of the last gs_batch_fetch_all (zero before one) */
+gs_status gs_batch_last_fetch(const gs_ctx* ctx, struct gs_batch_fetch_stats* out);
 /* slot i's message (why its problem was refused, or why its fetch failed) */
 size_t gs_batch_error(const gs_ctx* ctx, uint32_t i, char* buf, size_t len);
 /* counters and times of the last batch prepare / run */

@@ -20,13 +20,23 @@
 //            kernel: (R, TOPO, WIDE) of K4 and the lane-pair width of K1/K2.
 //            Five launches per group: cursors, rows, state reset, Solve,
 //            truncation.
+//  fetch_all every slot's result after one device pass: two launches
+//            (batch_fetch.hip: sizes, copy) pack the batched slots' records
+//            into one staging buffer (batch_fetch_layout.hpp), which comes
+//            back in one transfer (two the first time after a prepare); each
+//            slot is then checked and decoded by decode_result, the code the
+//            per-slot fetch ends in too, on up to 16 host threads.
 #include <atomic>
 #include <thread>
 #include <tuple>
 
+#include "batch_fetch_layout.hpp"
 #include "ctx.hpp"
 
 extern "C" uint32_t gsk_ffdw_wide(uint32_t W);
+// batch_fetch.hip: the records of n problems of a device array, packed into `staging`
+extern "C" hipError_t gsk_fetch_gather_batch(const gsd::DevProblem* ds, uint32_t n, uint32_t max_pods, void* staging,
+                                             uint64_t payload_cap, hipStream_t s);
 
 namespace gsc {
 
@@ -53,6 +63,17 @@ struct Batch {
   gsd::DevProblem* dev = nullptr;
   size_t dev_cap = 0;
   gs_batch_stats stats{};
+  // gs_batch_fetch_all: the staging buffer (device) and its pinned mirror; both
+  // only grow.  fetch_hint: the payload bytes the last fetch_all of this batch
+  // found (a run on the same upload finds the same): the next one's first
+  // transfer carries as many.
+  void* g_dev = nullptr;
+  size_t g_dev_cap = 0;
+  void* g_host = nullptr;
+  size_t g_host_cap = 0;
+  uint64_t fetch_hint = 0;
+  gs_batch_fetch_stats fstats{};
+  double fetch_gather_ms = 0, fetch_decode_ms = 0;  // the last fetch_all's device pass and decode (wall clock)
 };
 
 namespace {
@@ -130,6 +151,152 @@ void build_groups(gs_ctx* c, Batch& b) {
   b.dirty = false;
 }
 
+// gs_batch_fetch_all's device pass: the records of every slot of the device
+// array in the pinned mirror.  Two launches, and one transfer of the heads and
+// as much payload as the batch's last fetch_all found.  The payload's size is
+// known after the synchronisation: when there is more, as in the first call
+// after a prepare, a second transfer brings the rest; when there is more than
+// the staging buffer holds the copy kernel wrote nothing, the buffer grows and
+// the launches repeat.  Nothing here depends on how many slots there are.
+struct Gathered {
+  const gsbf::FetchHead* heads = nullptr;  // [order.size()]
+  const char* payload = nullptr;
+  uint64_t total = 0;  // payload bytes: all of them are in the mirror
+};
+constexpr uint64_t kFetchMinPayload = 1u << 20;
+
+Gathered gather_all(gs_ctx* c, Batch& b, gs_batch_fetch_stats& fs) {
+  const uint32_t ng = (uint32_t)b.order.size();
+  const uint64_t base = gsbf::payload_base(ng);
+  uint64_t worst = 0;
+  uint32_t max_pods = 0;
+  for (const gsd::DevProblem& d : b.host) {
+    worst += gsbf::worst_bytes(gsbf::FetchBounds{d.P, d.claim_cap});
+    max_pods = std::max(max_pods, d.P);
+  }
+  auto grow_dev = [&](uint64_t payload) {
+    const uint64_t need = base + payload;
+    if (need <= b.g_dev_cap) return;
+    if (b.g_dev) HIPCHK(hipFree(b.g_dev));
+    b.g_dev = nullptr;
+    b.g_dev_cap = 0;
+    const uint64_t want = need + need / 4;
+    HIPCHK(hipMalloc(&b.g_dev, want));
+    b.g_dev_cap = want;
+  };
+  // the mirror grows to what a call transfers; `keep` bytes of it survive
+  auto grow_host = [&](uint64_t bytes, uint64_t keep) {
+    if (bytes <= b.g_host_cap) return;
+    void* p = nullptr;
+    const uint64_t want = bytes + bytes / 4;
+    HIPCHK(hipHostMalloc(&p, want, hipHostMallocDefault));
+    if (keep) std::memcpy(p, b.g_host, keep);
+    if (b.g_host) (void)hipHostFree(b.g_host);
+    b.g_host = p;
+    b.g_host_cap = want;
+  };
+  b.fetch_hint = std::min(b.fetch_hint, worst);
+  grow_dev(std::max(b.fetch_hint, std::min(worst, kFetchMinPayload)));
+  float dev_ms = 0;
+  uint64_t cap = 0;  // payload bytes the staging buffer holds
+  auto launch = [&](uint64_t bytes) {
+    cap = (b.g_dev_cap - base) & ~(uint64_t)15u;
+    HIPCHK(hipEventRecord(c->ev[6], c->stream));
+    HIPCHK(gsk_fetch_gather_batch(b.dev, ng, max_pods, b.g_dev, cap, c->stream));
+    HIPCHK(hipEventRecord(c->ev[7], c->stream));
+    HIPCHK(hipMemcpyAsync(b.g_host, b.g_dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev[6], c->ev[7]));
+    dev_ms += ms;
+    fs.n_launches += 2;
+    fs.n_copies++;
+    fs.bytes += bytes;
+    const gsbf::FetchTop top = *(const gsbf::FetchTop*)b.g_host;
+    if (top.n != ng || top.total > worst || (top.total & 15u)) throw HipError{"gs_batch_fetch_all: corrupt gather total"};
+    return top.total;
+  };
+  const uint64_t first = base + b.fetch_hint;
+  grow_host(first, 0);
+  uint64_t total = launch(first);
+  if (total > cap) {
+    // the copy kernel wrote nothing: a buffer that holds the total, the launches again, everything in one transfer
+    grow_dev(total);
+    grow_host(base + total, 0);
+    if (launch(base + total) != total) throw HipError{"gs_batch_fetch_all: the gather total changed between two passes"};
+  } else if (total > b.fetch_hint) {
+    const uint64_t rest = total - b.fetch_hint;
+    grow_host(base + total, first);
+    HIPCHK(hipMemcpyAsync((char*)b.g_host + first, (const char*)b.g_dev + first, rest, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    fs.n_copies++;
+    fs.bytes += rest;
+  }
+  b.fetch_hint = total;
+  fs.device_ms = dev_ms;
+  Gathered g;
+  g.heads = (const gsbf::FetchHead*)((const char*)b.g_host + gsbf::kTopBytes);
+  g.payload = (const char*)b.g_host + base;
+  g.total = total;
+  return g;
+}
+
+// gs_fetch's status messages and counters for a gathered slot (h: its head,
+// pay: its payload in the mirror)
+gs_status decode_gathered(gs_ctx* c, const gsbf::FetchHead& h, const char* pay, gs_result* out) {
+  const auto& e = c->enc;
+  if (h.status == gsd::ST_CLAIMS)
+    return fail(c, GS_E_CAPACITY, "NodeClaim count exceeded the device capacity (" +
+                                      std::to_string(c->ch ? std::min<uint32_t>(c->dp.claim_cap, 65535) : c->dp.max_claims) +
+                                      " in-flight NodeClaims)");
+  if (h.status == gsd::ST_POD_COUNT)
+    return fail(c, GS_E_CAPACITY, "a NodeClaim would hold more than 65535 pods (16-bit pod count in LDS)");
+  if (h.status == gsd::ST_INTERNAL) return fail(c, GS_E_HIP, "ffd kernel reported an internal error (queue / channel bound)");
+  if (h.status != 0) return fail(c, GS_E_HIP, "ffd kernel reported an unknown status");
+  const gsbf::FetchRegions r = gsbf::regions(h.n_log, h.n_claims, h.qlen);
+  const SolveRecords rec{(const gsd::LogRec*)(pay + r.log),
+                         h.n_log,
+                         (const gsd::ClaimRec*)(pay + r.rec),
+                         (const uint32_t*)(pay + r.its),
+                         (const uint32_t*)(pay + r.nits),
+                         h.n_claims,
+                         (const uint32_t*)(pay + r.unplaced),
+                         h.qlen,
+                         nullptr,
+                         e.node_order.data()};
+  const gs_status ds = decode_result(c, rec, out);
+  if (ds != GS_OK) return ds;
+  c->ctrl.status = h.status;
+  c->ctrl.n_claims = h.n_claims;
+  c->ctrl.n_log = h.n_log;
+  c->ctrl.qhead = h.qhead;
+  c->ctrl.qlen = h.qlen;
+  out->checks = e.checks;
+  out->pops = h.pops;
+  out->cand_evals = h.cand_evals;
+  out->cand_full = h.cand_full;
+  out->claim_prefix = h.claim_prefix;
+  out->node_prefix = h.node_prefix;
+  // wall_clock64 runs at 100 MHz; ~0: the phase timers are not built in (-1)
+  auto phase_ms = [](uint64_t t) { return t == ~0ull ? -1.0 : (double)t * 1e-5; };
+  out->t_ffd_sort_ms = phase_ms(h.t_sort);
+  out->t_ffd_scan_ms = phase_ms(h.t_scan);
+  out->t_ffd_template_ms = phase_ms(h.t_tmpl);
+  out->sorts_fast = h.fast_sorts;
+  out->sorts_generic = h.generic_sorts;
+  out->words = e.W;
+  out->n_templates = e.T;
+  out->n_variants = e.V;
+  out->t_encode_ms = c->t_encode;
+  out->t_upload_ms = c->t_upload;
+  out->t_feas_ms = c->t_feas;
+  out->t_ffd_ms = c->t_ffd;
+  out->t_truncate_ms = c->t_trunc;
+  out->t_run_wall_ms = c->t_run_wall;
+  out->t_wall_ms = 0;
+  return GS_OK;
+}
+
 }  // namespace
 
 void batch_destroy(gs_ctx* c) {
@@ -138,6 +305,8 @@ void batch_destroy(gs_ctx* c) {
   for (auto& s : b->slots)
     if (s.c) free_slot(s.c);
   if (b->dev) (void)hipFree(b->dev);
+  if (b->g_dev) (void)hipFree(b->g_dev);
+  if (b->g_host) (void)hipHostFree(b->g_host);
   delete b;
   c->batch = nullptr;
 }
@@ -161,6 +330,9 @@ gs_status gs_batch_prepare(gs_ctx* c, const gs_problem* const* problems, uint32_
   b.prepared = b.ran = false;
   b.dirty = true;
   b.n = 0;
+  b.fetch_hint = 0;
+  b.fstats = gs_batch_fetch_stats{};
+  b.fetch_gather_ms = b.fetch_decode_ms = 0;
   while (b.slots.size() < n) {
     BatchSlot s;
     s.c = new gs_ctx();
@@ -314,6 +486,112 @@ gs_status gs_batch_fetch(gs_ctx* c, uint32_t i, gs_result* out) {
   if (s.status != GS_OK) return s.status;
   if (!c->batch->ran) return GS_E_INVALID;
   return gs_fetch(s.c, out);
+}
+
+gs_status gs_batch_fetch_all(gs_ctx* c, gs_result* out, gs_status* status) {
+  if (!c || !c->batch || !c->batch->prepared) return GS_E_INVALID;
+  Batch& b = *c->batch;
+  if (b.n && (!out || !status)) return fail(c, GS_E_INVALID, "gs_batch_fetch_all: NULL out or status");
+  if (!b.ran) return fail(c, GS_E_INVALID, "gs_batch_fetch_all: the batch has not run");
+  const auto t0 = Clock::now();
+  gs_batch_fetch_stats fs{};
+  fs.n_slots = b.n;
+  b.fetch_gather_ms = b.fetch_decode_ms = 0;
+  for (uint32_t i = 0; i < b.n; i++) {
+    status[i] = b.slots[i].status;
+    std::memset(&out[i], 0, sizeof(out[i]));
+  }
+  // the device array's slots that are still the batched run's (one that turned
+  // fallback stays in the array until the next run and is fetched alone)
+  std::vector<uint32_t> pos;  // positions to decode
+  for (uint32_t p = 0; p < b.order.size(); p++)
+    if (!b.slots[b.order[p]].fallback) pos.push_back(p);
+  if (!pos.empty()) {
+    Gathered g;
+    try {
+      HIPCHK(hipSetDevice(c->device));
+      g = gather_all(c, b, fs);
+    } catch (const HipError& e) {
+      return fail(c, GS_E_HIP, e.msg);
+    }
+    b.fetch_gather_ms = ms_since(t0);
+    const auto td = Clock::now();
+    const uint32_t ng = (uint32_t)b.order.size();
+    std::vector<gsbf::FetchBounds> bounds(ng);
+    for (uint32_t p = 0; p < ng; p++) bounds[p] = gsbf::FetchBounds{b.host[p].P, b.host[p].claim_cap};
+    std::vector<uint8_t> ok(ng, 0);
+    gsbf::validate(g.heads, bounds.data(), ng, g.total, g.total, ok.data());
+    // slots are independent (own encoding, own result storage, own message):
+    // decode on up to the 16 threads the prepare encodes on
+    std::atomic<uint32_t> next{0};
+    auto work = [&] {
+      for (;;) {
+        const uint32_t k = next.fetch_add(1);
+        if (k >= pos.size()) return;
+        const uint32_t p = pos[k], i = b.order[p];
+        gs_ctx* sc = b.slots[i].c;
+        if (!ok[p]) {
+          status[i] = fail(sc, GS_E_HIP, "gs_batch_fetch_all: corrupt gathered records");
+          continue;
+        }
+        status[i] = decode_gathered(sc, g.heads[p], g.payload + g.heads[p].off, &out[i]);
+      }
+    };
+    std::vector<std::thread> th;
+    const uint32_t nt = std::min<uint32_t>(kEncodeThreads, (uint32_t)pos.size());
+    for (uint32_t t = 1; t < nt; t++) th.emplace_back(work);
+    work();
+    for (auto& t : th) t.join();
+    for (uint32_t p : pos)
+      if (status[b.order[p]] == GS_OK) fs.n_decided++;
+    b.fetch_decode_ms = ms_since(td);
+  }
+  // the run's fallback slots: gs_fetch, as gs_batch_fetch does
+  for (uint32_t i = 0; i < b.n; i++) {
+    BatchSlot& s = b.slots[i];
+    if (s.status != GS_OK || !s.fallback) continue;
+    status[i] = gs_fetch(s.c, &out[i]);
+    if (status[i] != GS_OK) {
+      std::memset(&out[i], 0, sizeof(out[i]));
+      fs.n_copies++;
+      fs.bytes += sizeof(gsd::Ctrl);
+      continue;
+    }
+    const gsd::Ctrl& k = s.c->ctrl;
+    const uint32_t P = s.c->enc.P;
+    fs.n_copies += 1u + (k.n_log ? 1u : 0u) + (k.n_claims ? 3u : 0u) + (P ? 1u : 0u);
+    fs.bytes += sizeof(gsd::Ctrl) + (uint64_t)k.n_log * sizeof(gsd::LogRec) +
+                (uint64_t)k.n_claims * (sizeof(gsd::ClaimRec) + 61 * sizeof(uint32_t)) + (uint64_t)P * sizeof(uint32_t);
+    fs.n_per_slot++;
+  }
+  fs.wall_ms = ms_since(t0);
+  for (uint32_t i = 0; i < b.n; i++) {
+    if (status[i] != GS_OK) {
+      std::memset(&out[i], 0, sizeof(out[i]));
+      continue;
+    }
+    gs_ctx* sc = b.slots[i].c;
+    sc->t_fetch = fs.wall_ms;
+    out[i].t_fetch_ms = sc->t_fetch;
+    out[i].t_total_ms = sc->t_encode + sc->t_upload + sc->t_feas + sc->t_ffd + sc->t_trunc + sc->t_fetch;
+  }
+  b.fstats = fs;
+  return GS_OK;
+}
+
+gs_status gs_batch_last_fetch(const gs_ctx* c, gs_batch_fetch_stats* out) {
+  if (!c || !out || !c->batch || !c->batch->prepared) return GS_E_INVALID;
+  *out = c->batch->fstats;
+  return GS_OK;
+}
+
+// diagnostic (not in the public header): the last gs_batch_fetch_all's wall
+// clock up to the end of the device pass (out[0]) and of the decode (out[1]), ms
+gs_status gs_debug_batch_fetch_ms(const gs_ctx* c, double out[2]) {
+  if (!c || !out || !c->batch) return GS_E_INVALID;
+  out[0] = c->batch->fetch_gather_ms;
+  out[1] = c->batch->fetch_decode_ms;
+  return GS_OK;
 }
 
 size_t gs_batch_error(const gs_ctx* c, uint32_t i, char* buf, size_t len) {

@@ -177,7 +177,7 @@ class GsBatchStats(C.Structure):
 
 
 class GsBatchFetchStats(C.Structure):
-    """gs_batch_fetch_stats (gs_batch_consolidate_last_fetch; size checked against gs_batch_fetch_stats_size)"""
+    """gs_batch_fetch_stats (gs_batch_last_fetch, gs_batch_consolidate_last_fetch; size checked against gs_batch_fetch_stats_size)"""
     _fields_ = [("n_slots", _U32), ("n_decided", _U32), ("n_per_slot", _U32), ("n_launches", _U32),
                 ("n_copies", _U32), ("bytes", C.c_uint64), ("device_ms", C.c_double), ("wall_ms", C.c_double)]
 

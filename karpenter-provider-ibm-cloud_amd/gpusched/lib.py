@@ -19,7 +19,7 @@ EXPORTS = ["gs_create", "gs_destroy", "gs_prepare", "gs_run", "gs_fetch", "gs_so
            "gs_consolidate", "gs_consolidate_rerun", "gs_consolidation_results", "gs_consolidation_choose", "gs_feasibility_shard",
            "gs_feasibility_shard_device", "gs_rank_instance_types", "gs_create_filter", "gs_build_catalog", "gs_build_id",
            "gs_batch_prepare", "gs_batch_run", "gs_batch_fetch", "gs_batch_error", "gs_batch_last_run",
-           "gs_batch_stats_size",
+           "gs_batch_stats_size", "gs_batch_fetch_all", "gs_batch_last_fetch",
            "gs_batch_consolidate_prepare", "gs_batch_consolidate_run", "gs_batch_consolidate_fetch",
            "gs_batch_consolidate_results", "gs_batch_consolidate_error", "gs_batch_consolidate_last_run",
            "gs_batch_consolidate_fetch_all", "gs_batch_consolidate_last_fetch", "gs_batch_fetch_stats_size",
@@ -150,6 +150,10 @@ def load():
         L.gs_batch_last_run.restype = C.c_int
         L.gs_batch_stats_size.argtypes = []
         L.gs_batch_stats_size.restype = C.c_uint32
+        L.gs_batch_fetch_all.argtypes = [vp, C.POINTER(abi.GsResult), C.POINTER(C.c_int)]
+        L.gs_batch_fetch_all.restype = C.c_int
+        L.gs_batch_last_fetch.argtypes = [vp, C.POINTER(abi.GsBatchFetchStats)]
+        L.gs_batch_last_fetch.restype = C.c_int
         L.gs_batch_consolidate_prepare.argtypes = [vp, C.POINTER(C.POINTER(abi.GsConsolidation)), C.c_uint32,
                                                    C.POINTER(C.c_int)]
         L.gs_batch_consolidate_prepare.restype = C.c_int
@@ -324,6 +328,29 @@ class Solver:
         if st != abi.GS_OK:
             raise GpuSchedError(st, self.batch_error(i))
         return abi.result_to_dict(res, self.batch_problems[i]), res
+
+    def batch_fetch_all(self, raw=False):
+        """gs_batch_fetch_all: every slot's result from one device pass ->
+        (results, statuses).  results[i] is what batch_fetch(i) returns,
+        (dict, raw gs_result), or None where statuses[i] is not GS_OK
+        (batch_error(i) has the message).  raw=True returns the gs_result
+        array instead of the results (no Python-side copy)."""
+        n = len(self.batch_problems)
+        res = (abi.GsResult * max(n, 1))()
+        status = (C.c_int * max(n, 1))()
+        self._check(self.L.gs_batch_fetch_all(self.ctx, res, status))
+        statuses = [int(status[i]) for i in range(n)]
+        if raw:
+            return res, statuses
+        results = [(abi.result_to_dict(res[i], self.batch_problems[i]), res[i]) if statuses[i] == abi.GS_OK else None
+                   for i in range(n)]
+        return results, statuses
+
+    def batch_fetch_stats(self):
+        """gs_batch_last_fetch -> dict of the gs_batch_fetch_stats fields"""
+        out = abi.GsBatchFetchStats()
+        self._check(self.L.gs_batch_last_fetch(self.ctx, C.byref(out)))
+        return {name: getattr(out, name) for name, _ in abi.GsBatchFetchStats._fields_}
 
     def batch_stats(self):
         """gs_batch_last_run -> dict of the gs_batch_stats fields"""
