@@ -309,6 +309,14 @@ __device__ __forceinline__ void wsyncT() {
   wsync();
 }
 
+// wait for the wave's vector memory operations only (loads, stores and
+// atomics share vmcnt on gfx9 and retire in issue order); the LDS / scalar and
+// export counters keep their maxima.  Placed before a loop that issues
+// stores, it leaves no load pending at the loop's head: with one pending
+// there the compiler guards its register inside the loop with vmcnt(0),
+// which then also waits for the loop's own stores and atomics, every pass.
+__device__ __forceinline__ void wait_vmem() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+
 // readlane as an unsigned dword (the builtin returns int: widening it
 // directly would sign-extend a low dword with bit 31 set)
 __device__ __forceinline__ uint32_t rlane(uint32_t x, uint32_t i) {

@@ -1154,9 +1154,11 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
 
   // Solver-side global writes: the add log entry (lane 0) and, for a
   // requests-only Add, the no-return atomic adds of the requests (lanes
-  // r < min(R, 4)).  They are fire-and-forget: the next exact check's loads
-  // wait on the vector memory counter, which the wave's earlier stores and
-  // atomics precede.
+  // r < min(R, 4)).  Nothing waits for them by name, but they are not free of
+  // waits: they count on vmcnt with the wave's loads and retire in issue
+  // order, so a later wait for any load waits for them first (the next exact
+  // check's loads do; a load left pending across a loop of emits would make
+  // every pass drain them, which run mode's wait_vmem() at run entry avoids).
   auto emit = [&](uint32_t type, uint32_t idx, uint32_t pod, uint32_t var, uint32_t tgt, uint32_t rqd_, int64_t rql) {
     if (false) {  // never taken: it only keeps post among the closure's captures until post itself goes
       post(type, idx, pod, var, tgt, rqd_);
@@ -1295,8 +1297,21 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
           }
         };
         load_window();
+        // no vector-memory operation of the general path stays pending into
+        // the run: the loop issues a log store and request atomics per pod,
+        // and a wait for an older load inside it would wait for those too
+        wait_vmem();
         uint32_t lf = 0;  // lane of the claim the last Add raised
         bool dirty = false;
+        // where the run must stop popping: the general path's pop bound
+        // (pops + 1 > max_pops) and the end of the first pass (qhead + 1 == P)
+        // are both known here, and both come one nearer per placed pod, as
+        // qhead does: one stop value of qhead stands for the two
+        uint32_t qstop;
+        {
+          const uint64_t bp = max_pops - pops, bq = P - 1u - qhead;
+          qstop = qhead + (uint32_t)(bp < bq ? bp : bq);
+        }
         // the run's share of the candidate, fast-accept, CanAdd and pod
         // counters: uniform, summed in scalars and added to the counter lanes
         // once, where the run ends (whatever ends it)
@@ -1339,6 +1354,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             }
             base = modpos;
             load_window();
+            if (CH) wait_vmem();  // the window's HBM loads do not reach the back edge pending
             lf = 0;
           } else if (eo > lf + 1) {
             CTR(C_FAST, 1);
@@ -1359,7 +1375,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             CTR(C_RX_SPEC, 1);
             break;
           }
-          if (pops + 1 > max_pops || qhead + 1 == P) break;
+          if (qhead == qstop) break;
           // the scan from the infeasible-prefix bound (the last Add's
           // position): the first candidate must be a fast accept
           const uint32_t lo = modpos - base;
@@ -1376,27 +1392,49 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
           // general path's phase B checks the same batch; the first feasible
           // one wins, else the fast accept; with neither in the window the pod
           // leaves the run (the general path scans on past it)
-          bool xwin = false;
-          uint64_t x_nx[WREG] = {0, 0, 0, 0};
-          int64_t x_tot[RR], x_ma[RR];
-          uint32_t x_mrow[RR];
-          uint64_t x_zm = 0;
-#pragma unroll
-          for (uint32_t r = 0; r < RR; r++) {
-            x_tot[r] = 0;
-            x_ma[r] = 0;
-            x_mrow[r] = 0;
-          }
-          const uint64_t vzm = (uint64_t)rlane(run_rec, 14) | ((uint64_t)rlane(run_rec, 15) << 32);
-          const uint64_t vcm = (uint64_t)rlane(run_rec, 16) | ((uint64_t)rlane(run_rec, 17) << 32);
-          auto RQV = [&](uint32_t r) -> int64_t {
-            return (int64_t)((uint64_t)rlane(run_rec, 32 + 2 * r) | ((uint64_t)rlane(run_rec, 33 + 2 * r) << 32));
+          // Queue.Pop of the pod, for either outcome (first pass: the ring
+          // record at qhead).  The ring and s_ctl are LDS in every
+          // instantiation, so the wave's LDS order is all the hand-off needs;
+          // lane 0 releases the slot (it may be refilled) and posts the
+          // heartbeat in one section.
+          uint32_t pp = 0, pv = 0;
+          auto pop_pod = [&]() {
+            pp = rlane(pf_x, 0);
+            pv = rlane(pf_x, VR_DW - 1);
+            wsync();
+            qhead++;
+            qlen--;
+            pops++;
+            if (lane == 0) {
+              vst(&s_ctl[0], qhead);
+              if ((pops & 15) == 0) vst(&s_ctl[3], (uint32_t)pops);
+            }
+            pf_seq = vld(&s_ring_seq[qhead % RING]);
+            pf_x = lane < RING_DW ? vld(&s_ring[qhead % RING][lane]) : 0u;
           };
           if (!(fab & 1ull << fl)) {
             if (rlane(run_rec, 2) != 0) {  // free-key entries: the general path
               CTR(C_RX_SCAN, 1);
               break;
             }
+            // the check and its winner's Add are one region: its state
+            // (option words, totals, cursors, zone mask) is initialised and
+            // live here only, and a fast accept carries none of it
+            uint64_t x_nx[WREG] = {0, 0, 0, 0};
+            int64_t x_tot[RR], x_ma[RR];
+            uint32_t x_mrow[RR];
+            uint64_t x_zm = 0;
+#pragma unroll
+            for (uint32_t r = 0; r < RR; r++) {
+              x_tot[r] = 0;
+              x_ma[r] = 0;
+              x_mrow[r] = 0;
+            }
+            const uint64_t vzm = (uint64_t)rlane(run_rec, 14) | ((uint64_t)rlane(run_rec, 15) << 32);
+            const uint64_t vcm = (uint64_t)rlane(run_rec, 16) | ((uint64_t)rlane(run_rec, 17) << 32);
+            auto RQV = [&](uint32_t r) -> int64_t {
+              return (int64_t)((uint64_t)rlane(run_rec, 32 + 2 * r) | ((uint64_t)rlane(run_rec, 33 + 2 * r) << 32));
+            };
             const uint32_t mfl = fab ? ffs64(fab) : 64u;
             const uint64_t ex = lpb & ~fab & (mfl == 64 ? ~0ull : ((1ull << mfl) - 1ull));
             const HotKD KD = hot();
@@ -1483,78 +1521,70 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             const uint64_t fm = ballot64(feas);
             if (fm) {
               fl = ffs64(fm);
-              xwin = true;
-            } else if (fab) {
-              fl = mfl;
-            } else {
+              const uint32_t e = rlane(ow, fl);
+              if ((e & 0xFFFFu) == 0xFFFFu) {
+                status = 3;  // the u16 pod count would overflow
+                break;
+              }
+              pop_pod();
+              // NodeClaim.Add after the exact check, by the winning lane (as
+              // the general path's): options, requests, cursors, the exact
+              // slack / room codes, requirements; the window takes the codes
+              const uint32_t vctb = rlane(run_rec, 3);
+              if (lane == fl) {
+                const uint32_t j = ow >> 16;
+                ClaimRec* cr = KD.c_rec + j;
+                uint64_t* opts = KD.c_opts + (size_t)j * OW;
+#pragma unroll
+                for (uint32_t w = 0; w < WREG; w++)
+                  if (w < W) opts[w] = x_nx[w];
+                int64_t nt[RR];
+                uint32_t cu[RR];
+#pragma unroll
+                for (uint32_t r = 0; r < RR; r++) {
+                  nt[r] = x_tot[r] + RQV(r);
+                  cu[r] = x_mrow[r] - s_thoff[r] - r;
+                  cr->tot(r) = nt[r];
+                  cr->thr(r) = (uint16_t)cu[r];
+                }
+                wsl = pack_slack(HotRQ{KD.RQ}, x_ma, nt);
+                wrm = pack_room(thr, s_thoff, cu, nt, KD.RQ);
+                s_slk[j] = wsl;
+                s_rm[j] = wrm;
+                cr->zm = x_zm & vzm;
+                cr->cm &= vcm;
+                cr->ctb &= vctb;
+                ow = e + 1u;
+              }
+              dirty = true;
+              const uint32_t f = base + fl;
+              wsyncT<CH>();
+              emit(WQ_LOG, nlog, pp, pv, e >> 16, 0, 0);
+              nlog++;
+              rc_cand += M - modpos < 64 ? M - modpos : 64;
+              rc_alg += f + 1;
+              rc_pods++;
+#ifdef GS_CAT_TL
+              cat_n += lane == 0 ? 1ull : 0ull;
+#endif
+              hint = f;
+              modkind = MOD_INC;
+              modpos = f;
+              lf = fl;
+              continue;
+            }
+            if (!fab) {
               CTR(C_RX_SCAN, 1);
               break;
             }
+            fl = mfl;
           }
           const uint32_t e = rlane(ow, fl);
           if ((e & 0xFFFFu) == 0xFFFFu) {
             status = 3;  // the u16 pod count would overflow
             break;
           }
-          // Queue.Pop of the pod (first pass: the ring record at qhead)
-          const uint32_t x_rec = pf_x;
-          const uint32_t pp = rlane(x_rec, 0), pv = rlane(x_rec, VR_DW - 1);
-          wsyncT<CH>();
-          if (lane == 0) vst(&s_ctl[0], qhead + 1);  // the slot may be refilled
-          qhead++;
-          qlen--;
-          pops++;
-          if ((pops & 15) == 0 && lane == 0) vst(&s_ctl[3], (uint32_t)pops);
-          pf_seq = vld(&s_ring_seq[qhead % RING]);
-          pf_x = lane < RING_DW ? vld(&s_ring[qhead % RING][lane]) : 0u;
-          if (xwin) {
-            // NodeClaim.Add after the exact check, by the winning lane (as
-            // the general path's): options, requests, cursors, the exact
-            // slack / room codes, requirements; the window takes the codes
-            const HotKD KD = hot();
-            const uint32_t vctb = rlane(run_rec, 3);
-            if (lane == fl) {
-              const uint32_t j = ow >> 16;
-              ClaimRec* cr = KD.c_rec + j;
-              uint64_t* opts = KD.c_opts + (size_t)j * OW;
-#pragma unroll
-              for (uint32_t w = 0; w < WREG; w++)
-                if (w < W) opts[w] = x_nx[w];
-              int64_t nt[RR];
-              uint32_t cu[RR];
-#pragma unroll
-              for (uint32_t r = 0; r < RR; r++) {
-                nt[r] = x_tot[r] + RQV(r);
-                cu[r] = x_mrow[r] - s_thoff[r] - r;
-                cr->tot(r) = nt[r];
-                cr->thr(r) = (uint16_t)cu[r];
-              }
-              wsl = pack_slack(HotRQ{KD.RQ}, x_ma, nt);
-              wrm = pack_room(thr, s_thoff, cu, nt, KD.RQ);
-              s_slk[j] = wsl;
-              s_rm[j] = wrm;
-              cr->zm = x_zm & vzm;
-              cr->cm &= vcm;
-              cr->ctb &= vctb;
-              ow = e + 1u;
-            }
-            dirty = true;
-            const uint32_t f = base + fl;
-            wsyncT<CH>();
-            emit(WQ_LOG, nlog, pp, pv, e >> 16, 0, 0);
-            nlog++;
-            rc_cand += M - modpos < 64 ? M - modpos : 64;
-            rc_alg += f + 1;
-            rc_pods++;
-#ifdef GS_CAT_TL
-            cat_n += lane == 0 ? 1ull : 0ull;
-#endif
-            hint = f;
-            modkind = MOD_INC;
-            modpos = f;
-            lf = fl;
-            continue;
-          }
+          pop_pod();
           // fast accept: NodeClaim.Add changes the requests only; room and
           // slack of lane fl shrink by the request (lanes r < RQ re-quantize
           // resource r, packed across lanes 0..3 as in the general path)
