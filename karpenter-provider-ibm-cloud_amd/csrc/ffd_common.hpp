@@ -649,6 +649,32 @@ __device__ __forceinline__ uint32_t thr_search(const int64_t* thr, uint32_t n, u
   return lo;
 }
 
+// The exact check's threshold rows for narrow option rows (<= 4 words):
+// nx &= thr_set[mrow[r]] for every resource r.  All rows are loaded before any
+// is used, so they cost one memory round trip however many cursors move; a
+// load per moved cursor, under its lane's condition, is a dependent round trip
+// per resource.  Loading every row is exact: opts ⊆ thr_set[cur[r]]
+// (invariant of every Add), so the row of a cursor that stays narrows nothing,
+// and row mrow[r] = o + r + m exists for every m <= n.
+template <uint32_t RR>
+__device__ __forceinline__ void and_thr_rows(const uint64_t* thr_set, uint32_t OW, const uint32_t (&mrow)[RR],
+                                             uint64_t (&nx)[4]) {
+  uint4 t0[RR], t1[RR];
+#pragma unroll
+  for (uint32_t r = 0; r < RR; r++) {
+    const uint4* tq = (const uint4*)(thr_set + (size_t)mrow[r] * OW);
+    t0[r] = tq[0];
+    t1[r] = tq[1];
+  }
+#pragma unroll
+  for (uint32_t r = 0; r < RR; r++) {
+    nx[0] &= ((uint64_t)t0[r].y << 32) | t0[r].x;
+    nx[1] &= ((uint64_t)t0[r].w << 32) | t0[r].z;
+    nx[2] &= ((uint64_t)t1[r].y << 32) | t1[r].x;
+    nx[3] &= ((uint64_t)t1[r].w << 32) | t1[r].z;
+  }
+}
+
 // choosePivot's hint for sort.Slice over sc[0, M), M > 12: the (up to) nine
 // sampled keys read by nine lanes in one LDS round trip, the median-of-three
 // comparisons on scalars (same swap count as SeqSort::choose_pivot)

@@ -1172,6 +1172,12 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
     }
   };
 
+  // ClaimRec.ctb &= v by a no-return atomic.  No Solve kernel reads ctb (the
+  // Adds and the new-NodeClaim path write it, the host reads it after the
+  // Solve), so the winner's Add does not wait for a load of it; like emit()'s
+  // request atomics it follows the wave's earlier writes of the same word.
+  [[maybe_unused]] auto and_ctb = [](ClaimRec* cr, uint32_t v) { atomicAnd(&cr->ctb, v); };
+
   // uniform loop state (scalar registers)
   uint32_t qhead = 0, qlen = P, epoch = 1, M = 0, modkind = MOD_NONE, modpos = 0, nlog = 0, status = 0;
   bool wrapped = false;
@@ -1423,7 +1429,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
             uint64_t x_nx[WREG] = {0, 0, 0, 0};
             int64_t x_tot[RR], x_ma[RR];
             uint32_t x_mrow[RR];
-            uint64_t x_zm = 0;
+            uint64_t x_zm = 0, x_cm = 0;
 #pragma unroll
             for (uint32_t r = 0; r < RR; r++) {
               x_tot[r] = 0;
@@ -1447,7 +1453,6 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
               uint32_t cur[RR];
 #pragma unroll
               for (uint32_t r = 0; r < RR; r++) x_ma[r] = cr->maxa[r];
-              uint64_t x_cm;
               {
                 const uint4* q = (const uint4*)cr;
                 const uint4 h0 = q[0], h1 = q[1], h2 = q[2], h3 = q[3];
@@ -1489,17 +1494,7 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
                 if (mm[r] == cur[r] + 4 && mm[r] < n) mm[r] = thr_search(thr + o, n, mm[r], x_tot[r] + RQV(r));
                 x_mrow[r] = o + r + mm[r];
               }
-#pragma unroll
-              for (uint32_t r = 0; r < RR; r++) {
-                if (mm[r] != cur[r]) {
-                  const uint4* tq = (const uint4*)(KD.thr_set + (size_t)x_mrow[r] * OW);
-                  const uint4 t0 = tq[0], t1 = tq[1];
-                  x_nx[0] &= ((uint64_t)t0.y << 32) | t0.x;
-                  x_nx[1] &= ((uint64_t)t0.w << 32) | t0.z;
-                  x_nx[2] &= ((uint64_t)t1.y << 32) | t1.x;
-                  x_nx[3] &= ((uint64_t)t1.w << 32) | t1.z;
-                }
-              }
+              and_thr_rows(KD.thr_set, OW, x_mrow, x_nx);  // every resource's row, one round trip
               if (G != Gt) {
                 uint64_t off[WREG] = {};
                 for (uint64_t gm = G; gm; gm &= gm - 1) {
@@ -1552,8 +1547,8 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
                 s_slk[j] = wsl;
                 s_rm[j] = wrm;
                 cr->zm = x_zm & vzm;
-                cr->cm &= vcm;
-                cr->ctb &= vctb;
+                cr->cm = x_cm & vcm;  // (the header's cm: no load in the Add)
+                and_ctb(cr, vctb);
                 ow = e + 1u;
               }
               dirty = true;
@@ -2260,16 +2255,24 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
           uint64_t accw = 0;
           if (!WIDE) {
             // opts ⊆ thr_set[cur] (invariant of every Add): only a resource
-            // whose cursor moves narrows the options further
+            // whose cursor moves narrows the options further, and the row of
+            // one that stays narrows nothing.  The non-topology kernel loads
+            // every resource's row, all in one round trip; the topology one
+            // measured slower that way (C3 + 2.3 %) and keeps a load per moved
+            // cursor
+            if (!TOPO) {
+              and_thr_rows(HK.thr_set, OW, mrow, nx);
+            } else {
 #pragma unroll
-            for (uint32_t r = 0; r < RR; r++) {
-              if (mm[r] != cur[r]) {
-                const uint4* tq = (const uint4*)(HK.thr_set + (size_t)mrow[r] * OW);
-                const uint4 t0 = tq[0], t1 = tq[1];
-                nx[0] &= ((uint64_t)t0.y << 32) | t0.x;
-                nx[1] &= ((uint64_t)t0.w << 32) | t0.z;
-                nx[2] &= ((uint64_t)t1.y << 32) | t1.x;
-                nx[3] &= ((uint64_t)t1.w << 32) | t1.z;
+              for (uint32_t r = 0; r < RR; r++) {
+                if (mm[r] != cur[r]) {
+                  const uint4* tq = (const uint4*)(HK.thr_set + (size_t)mrow[r] * OW);
+                  const uint4 t0 = tq[0], t1 = tq[1];
+                  nx[0] &= ((uint64_t)t0.y << 32) | t0.x;
+                  nx[1] &= ((uint64_t)t0.w << 32) | t0.z;
+                  nx[2] &= ((uint64_t)t1.y << 32) | t1.x;
+                  nx[3] &= ((uint64_t)t1.w << 32) | t1.z;
+                }
               }
             }
             if (G != Gt) {
@@ -2417,7 +2420,10 @@ __global__ __launch_bounds__(128, 1) void ffdw_kernel(DevProblem d) {
           s_rm[j] = pack_room(thr, s_thoff, cu, nt, HK.RQ);
           cr->zm = zm & vzm;  // zm (dom_ct: cm) carries the topology narrowing
           cr->cm = cm & vcm;
-          cr->ctb &= vctb;
+          // (the narrow non-topology kernel alone: C3 and the C5 Solve measured
+          // slower with the atomic)
+          if (!TOPO && !WIDE) and_ctb(cr, vctb);
+          else cr->ctb &= vctb;
           if (TOPO) {
             // zone requirement after Add (+ the topology domain), then
             // <U> Topology.Record for every group selecting the pod
