@@ -727,6 +727,106 @@ typedef struct gs_feas_device {
 
 gs_status gs_feasibility_shard_device(gs_ctx* ctx, uint32_t word_begin, uint32_t word_end, gs_feas_device* out);
 
+/* ---- why each NodePool could not take a pod (Results.PodErrors' text) -------
+ * gs_result names the pods a Solve left unplaced; upstream's Results.PodErrors
+ * maps each of them to an error with one line per NodePool, which karpenter
+ * publishes as FailedScheduling events.  gs_explain gives, for every requested
+ * pod and every NodePool, the code of that line, from the data a gs_prepare
+ * left on the device: one kernel pass over the (pod variant, NodeClaim
+ * template) pairs of the requested pods, its own buffers, no gs_run needed and
+ * none disturbed (nor a gs_fetch or gs_feasibility before or after it).
+ *
+ * <U> restated from memory of karpenter v1.13, like the rest of the Solve:
+ * the order of the checks for one NodeClaimTemplate in Scheduler.add ->
+ * NodeClaim.CanAdd -> filterInstanceTypesByRequirements, and the chain of
+ * InstanceTypeFilterError.Error().  The first code that applies wins.
+ *
+ * R, F and O below range over the instance types gs_feasibility's rows start
+ * from: the template's options after NewScheduler's own filter, limited by the
+ * NodePool's limits as given.  Per option, R is
+ * it.Requirements.Intersects(template AND pod requirements), F is
+ * resources.Fits(daemon + pod, allocatable), O is an available offering
+ * compatible with the merged zone and capacity-type requirements.
+ *
+ * NOT modelled: topology (spread, pod affinity and anti-affinity), host
+ * ports, volumes, NodePool limits already consumed by the Solve, and the
+ * existing nodes.  A pod that only those keep out of a NodePool reads
+ * GS_WHY_STATE there: a NodeClaim opened from the NodePool for the pod alone
+ * takes it, so the cause lay in the Solve's state, which the library does not
+ * reconstruct.  Upstream's per-key detail inside "incompatible requirements"
+ * is not reproduced either. */
+enum {
+  GS_WHY_STATE = 0,             /* a fresh NodeClaim of this NodePool takes the pod (see above) */
+  GS_WHY_NO_OPTIONS = 1,        /* the NodePool kept no instance-type option at NewScheduler: upstream has no
+                                   template for it and no line in the pod's error */
+  GS_WHY_LIMITS = 2,            /* "all available instance types exceed limits for nodepool": options, but none
+                                   within the limits as given */
+  GS_WHY_TAINTS = 3,            /* "did not tolerate taint" */
+  GS_WHY_INCOMPATIBLE = 4,      /* "incompatible requirements": Requirements.Compatible(pod,
+                                   AllowUndefinedWellKnownLabels) against the template fails */
+  GS_WHY_MIN_VALUES = 5,        /* the minValues error: GS_MET_ALL, but those options miss a template minValues */
+  GS_WHY_IT_NONE = 6,           /* !R !F !O "no instance type met the scheduling requirements or had enough
+                                   resources or had a required offering" */
+  GS_WHY_IT_REQ_OR_FITS = 7,    /* !R !F "no instance type met the scheduling requirements or had enough resources" */
+  GS_WHY_IT_REQ_OR_OFFERING = 8,/* !R !O "no instance type met the scheduling requirements or had a required offering" */
+  GS_WHY_IT_FITS_OR_OFFERING = 9,/* !F !O "no instance type had enough resources or had a required offering" */
+  GS_WHY_IT_REQUIREMENTS = 10,  /* !R "no instance type met all requirements" */
+  GS_WHY_IT_RESOURCES = 11,     /* !F "no instance type has enough resources" */
+  GS_WHY_IT_OFFERING = 12,      /* !O "no instance type has the required offering" */
+  GS_WHY_IT_REQ_FITS_NO_OFFERING = 13, /* "no instance type which met the scheduling requirements and had enough
+                                   resources, had a required offering" */
+  GS_WHY_IT_FITS_OFFERING_NO_REQ = 14, /* "no instance type which had enough resources and the required offering met
+                                   the scheduling requirements" */
+  GS_WHY_IT_REQ_OFFERING_NO_FITS = 15, /* "no instance type which met the scheduling requirements and the required
+                                   offering had the required resources" */
+  GS_WHY_IT_TUPLE = 16,         /* "no instance type met the requirements/resources/offering tuple" */
+  GS_WHY_COUNT = 17
+};
+/* gs_explain_result.met: upstream's seven booleans, "some option ..." */
+enum {
+  GS_MET_REQUIREMENTS = 1u << 0,      /* ... met R */
+  GS_MET_FITS = 1u << 1,              /* ... met F */
+  GS_MET_OFFERING = 1u << 2,          /* ... met O */
+  GS_MET_REQ_FITS_ONLY = 1u << 3,     /* ... met exactly R and F */
+  GS_MET_REQ_OFFERING_ONLY = 1u << 4, /* ... met exactly R and O */
+  GS_MET_FITS_OFFERING_ONLY = 1u << 5,/* ... met exactly F and O */
+  GS_MET_ALL = 1u << 6                /* ... met all three */
+};
+/* gs_explain flags */
+#define GS_EXPLAIN_AS_GIVEN 1u /* judge the pod's first variant (the one gs_feasibility uses), not its last */
+typedef struct gs_explain_result {
+  uint32_t n_pods, n_nodepools;
+  const uint32_t* pods;   /* [n_pods] the list as asked (every pod, ascending, for pods == NULL) */
+  const uint8_t* cause;   /* [n_pods][n_nodepools] GS_WHY_* */
+  const uint8_t* met;     /* [n_pods][n_nodepools] GS_MET_*; 0 where the cause is decided before the instance
+                             types are looked at (NO_OPTIONS, LIMITS, TAINTS, INCOMPATIBLE) */
+  const int32_t* taint;   /* [n_pods][n_nodepools] GS_WHY_TAINTS: index into gs_problem.taints of the first taint, in
+                             the NodePool's own order, that the pod does not tolerate; otherwise -1 */
+  uint32_t n_variants;    /* distinct pod variants the kernel evaluated */
+  uint32_t reserved;
+  double t_kernel_ms;     /* HIP events around the explain kernels */
+  double t_total_ms;      /* wall clock of the call */
+  uint64_t d2h_bytes;     /* 4 per evaluated (variant, template) pair */
+} gs_explain_result;
+/* Explain n pods of the prepared problem (gs_prepare done; no gs_run needed).
+ * pods: indices into gs_problem.pods, any order, repeats allowed; pods == NULL
+ * with n == 0 means every pod.  pods may point into the error_pods of the
+ * context's last gs_result: gs_explain(ctx, res.error_pods, res.n_errors, 0, &why)
+ * is the intended call; the list is read before anything of the context's is
+ * overwritten and that gs_result stays valid (with n_errors == 0 there is
+ * nothing to ask: error_pods may then be NULL, which would read as every pod).
+ * flags 0: each pod is judged on its requirements after every relaxation
+ * Preferences.Relax can apply (its last variant: the attempt whose error
+ * upstream reports).  GS_EXPLAIN_AS_GIVEN: on its first variant.
+ * `out` is owned by the context until the next gs_explain, gs_prepare or
+ * gs_destroy.  GS_E_INVALID: NULL ctx or out, NULL pods with n > 0, nothing
+ * prepared, a pod index out of range, an unknown flag; the previous explain
+ * result stays valid.  n == 0 with non-NULL pods: GS_OK, empty tables, no
+ * device work.  A context with shards runs the call on the Solve's device. */
+gs_status gs_explain(gs_ctx* ctx, const uint32_t* pods, uint32_t n, uint32_t flags, gs_explain_result* out);
+/* sizeof the struct, for a binding's layout check */
+uint32_t gs_explain_result_size(void);
+
 /* Autoplacement ranking.  Replaces
  * IBMInstanceTypeProvider.FilterInstanceTypes (pkg/providers/common/instancetype/
  * instancetype.go:259-356) + rankInstanceTypes (:358-379); with every filter

@@ -654,6 +654,7 @@ void gs_destroy(gs_ctx* c) {
   if (c->stage) (void)hipHostFree(c->stage);
   create_filter_destroy(c);
   rank_batch_destroy(c);
+  explain_destroy(c);
   for (auto& e : c->ev)
     if (e) (void)hipEventDestroy(e);
   if (c->stream) (void)hipStreamDestroy(c->stream);

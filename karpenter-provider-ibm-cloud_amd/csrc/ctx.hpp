@@ -127,6 +127,7 @@ struct ConsBatch;  // batch_consolidate.hip: the slots of gs_batch_consolidate_*
 void batch_consolidate_destroy(gs_ctx* c);
 void create_filter_destroy(gs_ctx* c);  // filter.hip: frees gs_ctx::cf
 void rank_batch_destroy(gs_ctx* c);     // rank_batch.hip: frees gs_ctx::rank
+void explain_destroy(gs_ctx* c);        // explain.hip: frees gs_ctx::explain
 
 }  // namespace gsc
 namespace gsf {
@@ -134,6 +135,9 @@ struct State;  // filter.hip: the re-filter's arena and results, its resident ca
 }
 namespace gsrb {
 struct State;  // rank_batch.hip: the ranking's resident catalog and the runs' buffers
+}
+namespace gse {
+struct State;  // explain.hip: gs_explain's device buffers, staging and result storage
 }
 
 struct gs_ctx {
@@ -202,6 +206,7 @@ struct gs_ctx {
 
   gsf::State* cf = nullptr;  // gs_create_filter and gs_create_filter_prepare / _run (filter.hip)
   gsrb::State* rank = nullptr;  // gs_rank_prepare / _run (rank_batch.hip)
+  gse::State* explain = nullptr;  // gs_explain (explain.hip)
   // gs_build_catalog result storage
   std::vector<std::string> cat_strs, cat_reasons;
   std::vector<const char*> cat_ptrs, cat_reason_ptrs;

@@ -166,6 +166,10 @@ struct Encoded {
   // host-only, for decode
   std::vector<Reqs> tmpl_reqs;  // incl. hostname In[omega]
   std::vector<PodVariant> variants;  // per spec variant: pods with equal specs share them (var_sv)
+  // per template, its NodePool's taints in the NodePool's own order: (index
+  // into gs_problem.taints, taint class).  gs_explain names the first one a
+  // pod does not tolerate
+  std::vector<std::vector<std::pair<uint32_t, uint32_t>>> tmpl_taint_order;
 };
 
 // status + message

@@ -91,6 +91,13 @@ void Ctx::build_taint_classes() {
     return m;
   };
   for (uint32_t t = 0; t < e.T; t++) e.tmpl[t].taints = mask(tmpl_taints[t]);
+  e.tmpl_taint_order.assign(e.T, {});
+  for (uint32_t t = 0; t < e.T; t++) {
+    // taint_ids kept every taint of the NodePool (no reject list): position i is taints.begin + i
+    const uint32_t begin = p->nodepools[e.tmpl[t].np_index].taints.begin;
+    for (uint32_t i = 0; i < tmpl_taints[t].size(); i++)
+      e.tmpl_taint_order[t].emplace_back(begin + i, cls[tmpl_taints[t][i]]);
+  }
   for (uint32_t pos = 0; pos < e.NN; pos++) e.nodes[pos].taints = mask(node_taints[pos]);
   for (uint32_t v = 0; v < e.V; v++) {
     gsd::VarRec& vr = e.vars[v];

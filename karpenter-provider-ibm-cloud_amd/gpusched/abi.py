@@ -495,3 +495,34 @@ def rank_queries(queries):
         x.min_memory_gb = int(kw.get("min_memory_gb", 0))
         x.max_price = float(kw.get("max_price", 0.0))
     return arr
+
+
+# ------------------------------------------------------------------ gs_explain
+(GS_WHY_STATE, GS_WHY_NO_OPTIONS, GS_WHY_LIMITS, GS_WHY_TAINTS, GS_WHY_INCOMPATIBLE, GS_WHY_MIN_VALUES,
+ GS_WHY_IT_NONE, GS_WHY_IT_REQ_OR_FITS, GS_WHY_IT_REQ_OR_OFFERING, GS_WHY_IT_FITS_OR_OFFERING,
+ GS_WHY_IT_REQUIREMENTS, GS_WHY_IT_RESOURCES, GS_WHY_IT_OFFERING, GS_WHY_IT_REQ_FITS_NO_OFFERING,
+ GS_WHY_IT_FITS_OFFERING_NO_REQ, GS_WHY_IT_REQ_OFFERING_NO_FITS, GS_WHY_IT_TUPLE) = range(17)
+GS_WHY_COUNT = 17
+(GS_MET_REQUIREMENTS, GS_MET_FITS, GS_MET_OFFERING, GS_MET_REQ_FITS_ONLY, GS_MET_REQ_OFFERING_ONLY,
+ GS_MET_FITS_OFFERING_ONLY, GS_MET_ALL) = (1 << i for i in range(7))
+GS_EXPLAIN_AS_GIVEN = 1  # gs_explain flag: judge the pod's first variant, not its last
+
+
+class GsExplainResult(C.Structure):
+    """gs_explain_result (size checked against gs_explain_result_size)"""
+    _fields_ = [("n_pods", _U32), ("n_nodepools", _U32), ("pods", C.POINTER(C.c_uint32)),
+                ("cause", C.POINTER(C.c_uint8)), ("met", C.POINTER(C.c_uint8)), ("taint", C.POINTER(C.c_int32)),
+                ("n_variants", _U32), ("reserved", _U32), ("t_kernel_ms", C.c_double), ("t_total_ms", C.c_double),
+                ("d2h_bytes", C.c_uint64)]
+
+
+def explain_to_dict(res: GsExplainResult) -> dict:
+    """a gs_explain_result copied out of library memory: pods [n], cause / met /
+    taint [n][n_nodepools] and the call's counters"""
+    n, t = res.n_pods, res.n_nodepools
+    return {"pods": _arr(res.pods, n, np.uint32),
+            "cause": _arr(res.cause, n * t, np.uint8).reshape(n, t),
+            "met": _arr(res.met, n * t, np.uint8).reshape(n, t),
+            "taint": _arr(res.taint, n * t, np.int32).reshape(n, t),
+            "n_variants": int(res.n_variants), "t_kernel_ms": float(res.t_kernel_ms),
+            "t_total_ms": float(res.t_total_ms), "d2h_bytes": int(res.d2h_bytes)}

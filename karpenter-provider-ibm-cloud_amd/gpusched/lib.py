@@ -26,7 +26,7 @@ EXPORTS = ["gs_create", "gs_destroy", "gs_prepare", "gs_run", "gs_fetch", "gs_so
            "gs_create_filter_prepare", "gs_create_filter_run", "gs_create_filter_set_available",
            "gs_create_filter_last_run", "gs_create_filter_stats_size",
            "gs_rank_prepare", "gs_rank_run", "gs_rank_last_run", "gs_rank_query_size", "gs_rank_result_size",
-           "gs_rank_stats_size"]
+           "gs_rank_stats_size", "gs_explain", "gs_explain_result_size"]
 
 
 def source_digest():
@@ -173,6 +173,10 @@ def load():
         L.gs_batch_consolidate_last_fetch.restype = C.c_int
         L.gs_batch_fetch_stats_size.argtypes = []
         L.gs_batch_fetch_stats_size.restype = C.c_uint32
+        L.gs_explain.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.POINTER(abi.GsExplainResult)]
+        L.gs_explain.restype = C.c_int
+        L.gs_explain_result_size.argtypes = []
+        L.gs_explain_result_size.restype = C.c_uint32
         _lib = L
     return _lib
 
@@ -604,6 +608,26 @@ class Solver:
         res = abi.GsFeasResult()
         self._check(self.L.gs_feasibility(self.ctx, C.byref(res)))
         return abi.feas_to_dict(res), res
+
+    def explain(self, pods=None, as_given=False, raw=False):
+        """gs_explain on the prepared problem: why each NodePool could not take
+        each of `pods` (None: every pod; a list of indices; or a (pointer,
+        count) pair such as (res.error_pods, res.n_errors) straight from a
+        gs_result) -> abi.explain_to_dict's dict; as_given judges the pod's
+        first variant instead of its last; raw=True returns the
+        gs_explain_result (library memory) instead"""
+        res = abi.GsExplainResult()
+        if pods is None:
+            ptr, n = None, 0
+        elif isinstance(pods, tuple):
+            ptr, n = pods
+            if n == 0:  # an empty list, not "every pod": the pointer of an empty error list may be NULL
+                ptr = (C.c_uint32 * 1)()
+        else:
+            n = len(pods)
+            ptr = (C.c_uint32 * max(n, 1))(*[int(p) for p in pods])
+        self._check(self.L.gs_explain(self.ctx, ptr, n, abi.GS_EXPLAIN_AS_GIVEN if as_given else 0, C.byref(res)))
+        return res if raw else abi.explain_to_dict(res)
 
     def feasibility_shard(self, word_begin, word_end):
         """gs_feasibility_shard: the static matrix over instance-type words [begin, end)"""
