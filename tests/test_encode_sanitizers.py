@@ -25,6 +25,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+import resource_sweep
 from gpusched import abi, lib, synth
 from oracle import pyoracle
 from test_create_filter import CT_CASES, GIT_CASES, _git_problem, _kat_problem, random_catalog
@@ -73,6 +74,13 @@ def plain_harness(tmp_path_factory):
     return _build_harness(str(tmp_path_factory.mktemp("plain") / "encode_harness"), [])
 
 
+def _sweep_problems():
+    """every resource count 1..8 in both name layouts (tests/resource_sweep.py):
+    the plain problem and the general one (nodes, bound pods, spreads, minValues)"""
+    return [(f"{case}-{resource_sweep.pair_id(pair)}", resource_sweep.problem(case, *pair))
+            for pair in resource_sweep.PAIRS for case in ("plain", "general")]
+
+
 def _problems():
     out = []
     for s in range(24):
@@ -90,6 +98,7 @@ def _problems():
     out.append(("c1", synth.make_c1()))
     out.append(("c3_2k", synth.make_c3(n_pods=2000)))
     out.append(("c4_200", synth.make_c4(n_nodes=200, n_pending=5)))
+    out += _sweep_problems()
     return out
 
 
@@ -163,7 +172,8 @@ def test_encoding_independent_of_thread_count(plain_harness, tmp_path):
     order whatever the split"): status, message and the digest of every
     Encoded array (encode_harness -d) are the same on 1 and on 4 threads"""
     probs = ([synth.random_problem(s) for s in range(3)] + [synth.random_topology(s) for s in range(3)] +
-             [synth.random_relax(s) for s in range(2)] + [synth.random_consolidation(s) for s in range(2)])
+             [synth.random_relax(s) for s in range(2)] + [synth.random_consolidation(s) for s in range(2)] +
+             [p for _, p in _sweep_problems()])
     dumps = []
     for i, p in enumerate(probs):
         dumps.append(str(tmp_path / f"p{i}.gspd"))
