@@ -2,13 +2,17 @@
 // context, one workgroup each, in a number of kernel launches that does not
 // depend on how many they are.
 //
-// A slot is a child gs_ctx (the state prepare_one produces: encoding, arena,
-// DevProblem, result storage) that borrows the parent's stream and events, so
-// a batch of 4,096 slots holds no stream of its own.  The problems are encoded
-// on up to 16 host threads and uploaded one after another; the DevProblem
-// structs of the batch-eligible slots are then copied into one device array,
-// ordered by group, and every kernel of the Solve path reads its problem from
-// that array (batch_kernels.hip, ffd_wave_batch_r.hip).
+// A slot is a child gs_ctx (the state prepare_one produces) on the parent's
+// stream and events.  The slot, the state every batch keeps and the host
+// thread loop are batch_common.hpp's, shared with batch_consolidate.hip; every
+// buffer is a DevBuf / PinnedBuf, freed with the batch.  This unit holds what
+// is the Solve batch's own: eligibility, the groups, the run loop, the gather
+// and its decode.
+//
+// The problems are encoded on up to 16 host threads and uploaded one after
+// another; the DevProblem structs of the batch-eligible slots are then copied
+// into one device array, ordered by group, and every kernel of the Solve path
+// reads its problem from that array (batch_kernels.hip, ffd_wave_batch_r.hip).
 //
 //  eligible  the single-wave kernel with its claim state in LDS, on a context
 //            with neither GS_CFG_BLOCK_SOLVE nor GS_CFG_CLAIMS_HBM
@@ -26,12 +30,10 @@
 //            back in one transfer (two the first time after a prepare); each
 //            slot is then checked and decoded by decode_result, the code the
 //            per-slot fetch ends in too, on up to 16 host threads.
-#include <atomic>
-#include <thread>
 #include <tuple>
 
+#include "batch_common.hpp"
 #include "batch_fetch_layout.hpp"
-#include "ctx.hpp"
 
 extern "C" uint32_t gsk_ffdw_wide(uint32_t W);
 // batch_fetch.hip: the records of n problems of a device array, packed into `staging`
@@ -40,17 +42,10 @@ extern "C" hipError_t gsk_fetch_gather_batch(const gsd::DevProblem* ds, uint32_t
 
 namespace gsc {
 
-struct BatchSlot {
-  gs_ctx* c = nullptr;
-  gs_status status = GS_E_INVALID;
-  bool fallback = false;  // solved through gs_run
-};
+using BatchSlot = SlotCore;  // fallback: solved through gs_run
 
-struct Batch {
-  std::vector<BatchSlot> slots;  // only grows: a slot's arena and pinned staging are reused
-  uint32_t n = 0;                // slots of the current batch
-  bool prepared = false, ran = false;
-  bool dirty = true;             // the device array is out of date (a prepare, or a slot turned fallback)
+struct Batch : BatchBase<BatchSlot> {
+  bool dirty = true;  // the device array is out of date (a prepare, or a slot turned fallback)
   struct Group {
     uint32_t R, topo, wide, lp;
     uint32_t first = 0, count = 0;  // range of the device array
@@ -58,35 +53,18 @@ struct Batch {
     uint64_t max_cursors = 0, max_pairs = 0;
   };
   std::vector<Group> groups;
-  std::vector<uint32_t> order;       // device array position -> slot
-  std::vector<gsd::DevProblem> host; // the array's host image
-  gsd::DevProblem* dev = nullptr;
-  size_t dev_cap = 0;
-  gs_batch_stats stats{};
-  // gs_batch_fetch_all: the staging buffer (device) and its pinned mirror; both
-  // only grow.  fetch_hint: the payload bytes the last fetch_all of this batch
-  // found (a run on the same upload finds the same): the next one's first
-  // transfer carries as many.
-  void* g_dev = nullptr;
-  size_t g_dev_cap = 0;
-  void* g_host = nullptr;
-  size_t g_host_cap = 0;
+  std::vector<gsd::DevProblem> host;  // the device array's host image
+  const gsd::DevProblem* problems() const { return (const gsd::DevProblem*)dev.data(); }
+  // gs_batch_fetch_all: the payload bytes the last fetch_all of this batch found
+  // (a run on the same upload finds the same): the next one's first transfer
+  // carries as many
   uint64_t fetch_hint = 0;
-  gs_batch_fetch_stats fstats{};
   double fetch_gather_ms = 0, fetch_decode_ms = 0;  // the last fetch_all's device pass and decode (wall clock)
 };
 
 namespace {
 
 constexpr uint32_t kLaunchesPerGroup = 5;
-constexpr uint32_t kEncodeThreads = 16;
-
-void free_slot(gs_ctx* s) {
-  s->free_all();
-  if (s->arena) (void)hipFree(s->arena);
-  if (s->stage) (void)hipHostFree(s->stage);
-  delete s;  // the stream and the events are the parent's
-}
 
 // the dynamic LDS gsk_ffdw requests for a problem with its claim state in LDS
 uint32_t wave_lds(const gsd::DevProblem& d) {
@@ -102,16 +80,9 @@ bool eligible(const gs_ctx* parent, const BatchSlot& s) {
 }
 
 void copy_to_device(gs_ctx* c, Batch& b, size_t n) {
-  if (n > b.dev_cap) {
-    if (b.dev) HIPCHK(hipFree(b.dev));
-    b.dev = nullptr;
-    b.dev_cap = 0;
-    const size_t want = n + n / 4;
-    HIPCHK(hipMalloc((void**)&b.dev, want * sizeof(gsd::DevProblem)));
-    b.dev_cap = want;
-  }
+  b.dev.reserve(n * sizeof(gsd::DevProblem));
   if (n) {
-    HIPCHK(hipMemcpyAsync(b.dev, b.host.data(), n * sizeof(gsd::DevProblem), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b.dev.data(), b.host.data(), n * sizeof(gsd::DevProblem), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
 }
@@ -174,37 +145,17 @@ Gathered gather_all(gs_ctx* c, Batch& b, gs_batch_fetch_stats& fs) {
     worst += gsbf::worst_bytes(gsbf::FetchBounds{d.P, d.claim_cap});
     max_pods = std::max(max_pods, d.P);
   }
-  auto grow_dev = [&](uint64_t payload) {
-    const uint64_t need = base + payload;
-    if (need <= b.g_dev_cap) return;
-    if (b.g_dev) HIPCHK(hipFree(b.g_dev));
-    b.g_dev = nullptr;
-    b.g_dev_cap = 0;
-    const uint64_t want = need + need / 4;
-    HIPCHK(hipMalloc(&b.g_dev, want));
-    b.g_dev_cap = want;
-  };
-  // the mirror grows to what a call transfers; `keep` bytes of it survive
-  auto grow_host = [&](uint64_t bytes, uint64_t keep) {
-    if (bytes <= b.g_host_cap) return;
-    void* p = nullptr;
-    const uint64_t want = bytes + bytes / 4;
-    HIPCHK(hipHostMalloc(&p, want, hipHostMallocDefault));
-    if (keep) std::memcpy(p, b.g_host, keep);
-    if (b.g_host) (void)hipHostFree(b.g_host);
-    b.g_host = p;
-    b.g_host_cap = want;
-  };
+  // (the mirror grows to what a call transfers; reserve_keep's `keep` bytes of it survive)
   b.fetch_hint = std::min(b.fetch_hint, worst);
-  grow_dev(std::max(b.fetch_hint, std::min(worst, kFetchMinPayload)));
+  b.g_dev.reserve(base + std::max(b.fetch_hint, std::min(worst, kFetchMinPayload)));
   float dev_ms = 0;
   uint64_t cap = 0;  // payload bytes the staging buffer holds
   auto launch = [&](uint64_t bytes) {
-    cap = (b.g_dev_cap - base) & ~(uint64_t)15u;
+    cap = (b.g_dev.capacity() - base) & ~(uint64_t)15u;
     HIPCHK(hipEventRecord(c->ev[6], c->stream));
-    HIPCHK(gsk_fetch_gather_batch(b.dev, ng, max_pods, b.g_dev, cap, c->stream));
+    HIPCHK(gsk_fetch_gather_batch(b.problems(), ng, max_pods, b.g_dev.data(), cap, c->stream));
     HIPCHK(hipEventRecord(c->ev[7], c->stream));
-    HIPCHK(hipMemcpyAsync(b.g_host, b.g_dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(b.g_host.data(), b.g_dev.data(), bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, c->ev[6], c->ev[7]));
@@ -212,22 +163,22 @@ Gathered gather_all(gs_ctx* c, Batch& b, gs_batch_fetch_stats& fs) {
     fs.n_launches += 2;
     fs.n_copies++;
     fs.bytes += bytes;
-    const gsbf::FetchTop top = *(const gsbf::FetchTop*)b.g_host;
+    const gsbf::FetchTop top = *(const gsbf::FetchTop*)b.g_host.data();
     if (top.n != ng || top.total > worst || (top.total & 15u)) throw HipError{"gs_batch_fetch_all: corrupt gather total"};
     return top.total;
   };
   const uint64_t first = base + b.fetch_hint;
-  grow_host(first, 0);
+  b.g_host.reserve_keep(first, 0);
   uint64_t total = launch(first);
   if (total > cap) {
     // the copy kernel wrote nothing: a buffer that holds the total, the launches again, everything in one transfer
-    grow_dev(total);
-    grow_host(base + total, 0);
+    b.g_dev.reserve(base + total);
+    b.g_host.reserve_keep(base + total, 0);
     if (launch(base + total) != total) throw HipError{"gs_batch_fetch_all: the gather total changed between two passes"};
   } else if (total > b.fetch_hint) {
     const uint64_t rest = total - b.fetch_hint;
-    grow_host(base + total, first);
-    HIPCHK(hipMemcpyAsync((char*)b.g_host + first, (const char*)b.g_dev + first, rest, hipMemcpyDeviceToHost, c->stream));
+    b.g_host.reserve_keep(base + total, first);
+    HIPCHK(hipMemcpyAsync((char*)b.g_host.data() + first, (const char*)b.g_dev.data() + first, rest, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     fs.n_copies++;
     fs.bytes += rest;
@@ -235,8 +186,8 @@ Gathered gather_all(gs_ctx* c, Batch& b, gs_batch_fetch_stats& fs) {
   b.fetch_hint = total;
   fs.device_ms = dev_ms;
   Gathered g;
-  g.heads = (const gsbf::FetchHead*)((const char*)b.g_host + gsbf::kTopBytes);
-  g.payload = (const char*)b.g_host + base;
+  g.heads = (const gsbf::FetchHead*)((const char*)b.g_host.data() + gsbf::kTopBytes);
+  g.payload = (const char*)b.g_host.data() + base;
   g.total = total;
   return g;
 }
@@ -300,14 +251,7 @@ gs_status decode_gathered(gs_ctx* c, const gsbf::FetchHead& h, const char* pay, 
 }  // namespace
 
 void batch_destroy(gs_ctx* c) {
-  Batch* b = c->batch;
-  if (!b) return;
-  for (auto& s : b->slots)
-    if (s.c) free_slot(s.c);
-  if (b->dev) (void)hipFree(b->dev);
-  if (b->g_dev) (void)hipFree(b->g_dev);
-  if (b->g_host) (void)hipHostFree(b->g_host);
-  delete b;
+  delete c->batch;  // its slots and buffers with it
   c->batch = nullptr;
 }
 
@@ -333,46 +277,26 @@ gs_status gs_batch_prepare(gs_ctx* c, const gs_problem* const* problems, uint32_
   b.fetch_hint = 0;
   b.fstats = gs_batch_fetch_stats{};
   b.fetch_gather_ms = b.fetch_decode_ms = 0;
-  while (b.slots.size() < n) {
-    BatchSlot s;
-    s.c = new gs_ctx();
-    s.c->device = c->device;
-    s.c->cfg_flags = c->cfg_flags;
-    s.c->stream = c->stream;
-    std::copy(std::begin(c->ev), std::end(c->ev), std::begin(s.c->ev));
-    b.slots.push_back(s);
-  }
+  b.ensure_slots(c, n);
   // encode on up to 16 host threads (the encoder's own loops share its pool)
-  std::atomic<uint32_t> next{0};
-  auto work = [&] {
-    for (;;) {
-      const uint32_t i = next.fetch_add(1);
-      if (i >= n) return;
-      BatchSlot& s = b.slots[i];
-      gs_ctx* sc = s.c;
-      sc->prepared = sc->ran = false;
-      sc->cons_ready = false;
-      sc->err.clear();
-      s.fallback = false;
-      if (!problems[i]) {
-        s.status = fail(sc, GS_E_INVALID, "NULL problem");
-        continue;
-      }
-      const auto te = Clock::now();
-      gsh::Err er = gsh::encode(problems[i], sc->enc);
-      sc->t_encode = ms_since(te);
-      if (er.code == GS_OK) er = capacity_check(sc->enc);
-      s.status = er.code == GS_OK ? GS_OK : fail(sc, er.code, er.msg);
-      sc->n_nodepools = problems[i]->n_nodepools;
+  parallel_for(n, kEncodeThreads, [&](uint32_t i) {
+    BatchSlot& s = b.slots[i];
+    gs_ctx* sc = s.c;
+    sc->prepared = sc->ran = false;
+    sc->cons_ready = false;
+    sc->err.clear();
+    s.fallback = false;
+    if (!problems[i]) {
+      s.status = fail(sc, GS_E_INVALID, "NULL problem");
+      return;
     }
-  };
-  {
-    std::vector<std::thread> th;
-    const uint32_t nt = std::min<uint32_t>(kEncodeThreads, n);
-    for (uint32_t t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto& t : th) t.join();
-  }
+    const auto te = Clock::now();
+    gsh::Err er = gsh::encode(problems[i], sc->enc);
+    sc->t_encode = ms_since(te);
+    if (er.code == GS_OK) er = capacity_check(sc->enc);
+    s.status = er.code == GS_OK ? GS_OK : fail(sc, er.code, er.msg);
+    sc->n_nodepools = problems[i]->n_nodepools;
+  });
   // upload the accepted slots, then gather every slot's first-pass queue
   // records in one launch
   uint32_t accepted = 0;
@@ -401,13 +325,13 @@ gs_status gs_batch_prepare(gs_ctx* c, const gs_problem* const* problems, uint32_
       accepted++;
     }
     copy_to_device(c, b, all.size());
-    HIPCHK(gsk_queue_records_batch(b.dev, (uint32_t)all.size(), max_pods, c->stream));
+    HIPCHK(gsk_queue_records_batch(b.problems(), (uint32_t)all.size(), max_pods, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   } catch (const HipError& e) {
-    for (uint32_t i = 0; i < n; i++) status[i] = b.slots[i].status;
+    b.copy_status(status, n);
     return fail(c, GS_E_HIP, e.msg);
   }
-  for (uint32_t i = 0; i < n; i++) status[i] = b.slots[i].status;
+  b.copy_status(status, n);
   b.n = n;
   b.prepared = true;
   b.stats = gs_batch_stats{};
@@ -430,7 +354,7 @@ gs_status gs_batch_run(gs_ctx* c) {
     if (!b.groups.empty()) {
       HIPCHK(hipEventRecord(c->ev[6], c->stream));
       for (const Batch::Group& g : b.groups) {
-        const gsd::DevProblem* ds = b.dev + g.first;
+        const gsd::DevProblem* ds = b.problems() + g.first;
         HIPCHK(gsk_feas_batch(ds, g.count, g.lp, g.max_cursors, g.max_pairs, c->stream));
         HIPCHK(gsk_init_state_batch(ds, g.count, c->stream));
         HIPCHK(gsk_ffdw_batch(ds, g.count, g.R, g.topo, g.wide, g.lds, c->stream));
@@ -497,10 +421,8 @@ gs_status gs_batch_fetch_all(gs_ctx* c, gs_result* out, gs_status* status) {
   gs_batch_fetch_stats fs{};
   fs.n_slots = b.n;
   b.fetch_gather_ms = b.fetch_decode_ms = 0;
-  for (uint32_t i = 0; i < b.n; i++) {
-    status[i] = b.slots[i].status;
-    std::memset(&out[i], 0, sizeof(out[i]));
-  }
+  b.copy_status(status, b.n);
+  if (b.n) std::memset(out, 0, (size_t)b.n * sizeof(*out));
   // the device array's slots that are still the batched run's (one that turned
   // fallback stays in the array until the next run and is fetched alone)
   std::vector<uint32_t> pos;  // positions to decode
@@ -523,25 +445,14 @@ gs_status gs_batch_fetch_all(gs_ctx* c, gs_result* out, gs_status* status) {
     gsbf::validate(g.heads, bounds.data(), ng, g.total, g.total, ok.data());
     // slots are independent (own encoding, own result storage, own message):
     // decode on up to the 16 threads the prepare encodes on
-    std::atomic<uint32_t> next{0};
-    auto work = [&] {
-      for (;;) {
-        const uint32_t k = next.fetch_add(1);
-        if (k >= pos.size()) return;
-        const uint32_t p = pos[k], i = b.order[p];
-        gs_ctx* sc = b.slots[i].c;
-        if (!ok[p]) {
-          status[i] = fail(sc, GS_E_HIP, "gs_batch_fetch_all: corrupt gathered records");
-          continue;
-        }
+    parallel_for((uint32_t)pos.size(), kEncodeThreads, [&](uint32_t k) {
+      const uint32_t p = pos[k], i = b.order[p];
+      gs_ctx* sc = b.slots[i].c;
+      if (!ok[p])
+        status[i] = fail(sc, GS_E_HIP, "gs_batch_fetch_all: corrupt gathered records");
+      else
         status[i] = decode_gathered(sc, g.heads[p], g.payload + g.heads[p].off, &out[i]);
-      }
-    };
-    std::vector<std::thread> th;
-    const uint32_t nt = std::min<uint32_t>(kEncodeThreads, (uint32_t)pos.size());
-    for (uint32_t t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto& t : th) t.join();
+    });
     for (uint32_t p : pos)
       if (status[b.order[p]] == GS_OK) fs.n_decided++;
     b.fetch_decode_ms = ms_since(td);
@@ -580,9 +491,7 @@ gs_status gs_batch_fetch_all(gs_ctx* c, gs_result* out, gs_status* status) {
 }
 
 gs_status gs_batch_last_fetch(const gs_ctx* c, gs_batch_fetch_stats* out) {
-  if (!c || !out || !c->batch || !c->batch->prepared) return GS_E_INVALID;
-  *out = c->batch->fstats;
-  return GS_OK;
+  return batch_last_fetch(c ? c->batch : nullptr, out);
 }
 
 // diagnostic (not in the public header): the last gs_batch_fetch_all's wall
@@ -595,14 +504,11 @@ gs_status gs_debug_batch_fetch_ms(const gs_ctx* c, double out[2]) {
 }
 
 size_t gs_batch_error(const gs_ctx* c, uint32_t i, char* buf, size_t len) {
-  if (!c || !c->batch || i >= c->batch->n) return 0;
-  return gs_last_error(c->batch->slots[i].c, buf, len);
+  return batch_error(c ? c->batch : nullptr, i, buf, len);
 }
 
 gs_status gs_batch_last_run(const gs_ctx* c, gs_batch_stats* out) {
-  if (!c || !out || !c->batch || !c->batch->prepared) return GS_E_INVALID;
-  *out = c->batch->stats;
-  return GS_OK;
+  return batch_last_run(c ? c->batch : nullptr, out);
 }
 
 }  // extern "C"

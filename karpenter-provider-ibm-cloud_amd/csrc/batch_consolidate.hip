@@ -2,15 +2,19 @@
 // simulations of many independent clusters on one context, in a number of
 // device operations that does not depend on how many clusters they are.
 //
-// A slot is a child gs_ctx as in batch.cpp (it borrows the parent's stream
-// and events) holding what gs_consolidate leaves resident: the input copy,
-// the encoding, the plan, the arena and the pinned result staging.  Prepare
-// runs gs_consolidate's host steps per slot (consolidate.cpp cons_*: check,
-// take + encode and plan the sets on up to 16 host threads, then the grid plan
-// and the upload one after another), copies the DevProblem structs of the
-// slots with simulations into one device array ordered by group, followed by
-// each slot's workgroup count, and that is the only copy: a run launches
-// kernels only.
+// A slot is a child gs_ctx as in batch.cpp (batch_common.hpp: the slot core,
+// the state every batch keeps, the host thread loop) holding what
+// gs_consolidate leaves resident: the input copy, the encoding, the plan, the
+// arena and the pinned result staging.  This unit holds what is the
+// consolidation batch's own: group keys, eligibility, the run loop, the
+// gather and its validation.
+//
+// Prepare runs gs_consolidate's host steps per slot (consolidate.cpp cons_*:
+// check, take + encode and plan the sets on up to 16 host threads, then the
+// grid plan and the upload one after another), copies the DevProblem structs
+// of the slots with simulations into one device array ordered by group,
+// followed by each slot's workgroup count, and that is the only copy: a run
+// launches kernels only.
 //
 //  group     the slots that need the same instantiation of every kernel:
 //            (R, general or not) of the simulation kernel, the lane-pair width
@@ -34,29 +38,21 @@
 //            into one staging buffer, which comes back in one transfer (two
 //            the first time after a prepare); cons_decide_records then decides each slot from its
 //            records, the code the per-slot fetch ends in too.
-#include <atomic>
-#include <thread>
 #include <tuple>
 
-#include "ctx.hpp"
+#include "batch_common.hpp"
 
 namespace gsc {
 
-struct ConsSlot {
-  gs_ctx* c = nullptr;
-  gs_status status = GS_E_INVALID;
-  bool grouped = false;   // in the device array: the batched launches cover it
-  bool fallback = false;  // has simulations the batched launches do not cover
-  bool fetched = false;   // copied back and decided since the last run
+struct ConsSlot : SlotCore {  // fallback: has simulations the batched launches do not cover
+  bool grouped = false;  // in the device array: the batched launches cover it
+  bool fetched = false;  // copied back and decided since the last run
   gs_status fetch_status = GS_OK;
 };
 
-struct ConsBatch {
-  std::vector<ConsSlot> slots;  // only grows: a slot's arena and pinned staging are reused
-  uint32_t n = 0;               // slots of the current batch
-  bool prepared = false, ran = false;
-  uint32_t nt = 256;            // the batch's simulation workgroup shape
-  uint32_t epoch = 0;           // the last overlay stamp prefix drawn (1..4095)
+struct ConsBatch : BatchBase<ConsSlot> {
+  uint32_t nt = 256;   // the batch's simulation workgroup shape
+  uint32_t epoch = 0;  // the last overlay stamp prefix drawn (1..4095)
   struct Group {
     uint32_t R, general, lp, mv;
     uint32_t first = 0, count = 0;  // range of the device array
@@ -64,27 +60,18 @@ struct ConsBatch {
     uint64_t max_cursors = 0, max_pairs = 0;
   };
   std::vector<Group> groups;
-  std::vector<uint32_t> order;  // device array position -> slot
-  // the device image: order.size() DevProblem, then order.size() workgroup
+  // the device image (dev): order.size() DevProblem, then order.size() workgroup
   // counts, then each slot's first record in fetch_all's simulation table
-  void* dev = nullptr;
-  size_t dev_cap = 0;
-  const gsd::DevProblem* problems() const { return (const gsd::DevProblem*)dev; }
-  const uint32_t* blocks() const { return (const uint32_t*)((const char*)dev + order.size() * sizeof(gsd::DevProblem)); }
+  const gsd::DevProblem* problems() const { return (const gsd::DevProblem*)dev.data(); }
+  const uint32_t* blocks() const { return (const uint32_t*)(problems() + order.size()); }
   const uint32_t* sim_base() const { return blocks() + order.size(); }
-  gs_batch_stats stats{};
-  // gs_batch_consolidate_fetch_all: the staging buffer (device) and its pinned
-  // mirror; both only grow.  Layout: a 64-B head whose first word is the option
+  // gs_batch_consolidate_fetch_all: the staging buffer (g_dev) and its pinned
+  // mirror (g_host).  Layout: a 64-B head whose first word is the option
   // cursor, SlotOut[order.size()], SimOut[n_sims], then the option region
   // (60 per simulation on the device; the mirror holds what a call transfers).
   std::vector<uint32_t> h_sim_base;  // device array position -> first record
   uint64_t n_sims = 0;               // simulations of the grouped slots
   uint32_t opt_hint = 0;             // options the last fetch_all of this batch found: the next one's first transfer carries as many
-  void* g_dev = nullptr;
-  size_t g_dev_cap = 0;
-  void* g_host = nullptr;
-  size_t g_host_cap = 0;
-  gs_batch_fetch_stats fstats{};
 };
 constexpr size_t kGatherHead = 64;
 // more simulations than the 32-bit option offsets address: no gathered path
@@ -92,15 +79,7 @@ constexpr uint64_t kGatherMaxSims = 1ull << 26;
 
 namespace {
 
-constexpr uint32_t kEncodeThreads = 16;
 using GroupKey = std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>;
-
-void free_slot(gs_ctx* s) {
-  s->free_all();
-  if (s->arena) (void)hipFree(s->arena);
-  if (s->stage) (void)hipHostFree(s->stage);
-  delete s;  // the stream and the events are the parent's
-}
 
 GroupKey key_of(const gsh::Encoded& e) {
   const uint32_t general = (e.TG || e.any_mv || e.any_vol) ? 1u : 0u;
@@ -163,20 +142,13 @@ void build_groups(gs_ctx* c, ConsBatch& b) {
   }
   const size_t n = b.order.size(), bytes = n * (sizeof(gsd::DevProblem) + 2 * sizeof(uint32_t));
   if (!n) return;
-  if (bytes > b.dev_cap) {
-    if (b.dev) HIPCHK(hipFree(b.dev));
-    b.dev = nullptr;
-    b.dev_cap = 0;
-    const size_t want = bytes + bytes / 4;
-    HIPCHK(hipMalloc(&b.dev, want));
-    b.dev_cap = want;
-  }
+  b.dev.reserve(bytes);
   std::vector<char> image(bytes);
   std::memcpy(image.data(), problems.data(), n * sizeof(gsd::DevProblem));
   std::memcpy(image.data() + n * sizeof(gsd::DevProblem), blocks.data(), n * sizeof(uint32_t));
   // (meaningless past kGatherMaxSims simulations, where fetch_all does not gather)
   std::memcpy(image.data() + n * (sizeof(gsd::DevProblem) + sizeof(uint32_t)), b.h_sim_base.data(), n * sizeof(uint32_t));
-  HIPCHK(hipMemcpyAsync(b.dev, image.data(), bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(b.dev.data(), image.data(), bytes, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
 }
 
@@ -221,29 +193,12 @@ Gathered gather_all(gs_ctx* c, ConsBatch& b, gs_batch_fetch_stats& fs) {
   const size_t recs_off = kGatherHead + ng * sizeof(gsd::SlotOut);
   const size_t opts_off = recs_off + b.n_sims * sizeof(gsd::SimOut);
   const size_t dev_bytes = opts_off + b.n_sims * gsd::SIM_OPTS_MAX * sizeof(gsd::OptPair);
-  if (dev_bytes > b.g_dev_cap) {
-    if (b.g_dev) HIPCHK(hipFree(b.g_dev));
-    b.g_dev = nullptr;
-    b.g_dev_cap = 0;
-    const size_t want = dev_bytes + dev_bytes / 4;
-    HIPCHK(hipMalloc(&b.g_dev, want));
-    b.g_dev_cap = want;
-  }
-  // the mirror grows to what a call transfers; `keep` bytes of it survive
-  auto grow_host = [&](size_t bytes, size_t keep) {
-    if (bytes <= b.g_host_cap) return;
-    void* p = nullptr;
-    const size_t want = bytes + bytes / 4;
-    HIPCHK(hipHostMalloc(&p, want, hipHostMallocDefault));
-    if (keep) std::memcpy(p, b.g_host, keep);
-    if (b.g_host) (void)hipHostFree(b.g_host);
-    b.g_host = p;
-    b.g_host_cap = want;
-  };
+  b.g_dev.reserve(dev_bytes);
+  // (the mirror grows to what a call transfers; reserve_keep's `keep` bytes of it survive)
   b.opt_hint = (uint32_t)std::min<uint64_t>(b.opt_hint, b.n_sims * gsd::SIM_OPTS_MAX);  // within the device region
   const size_t first = opts_off + (size_t)b.opt_hint * sizeof(gsd::OptPair);
-  grow_host(first, 0);
-  char* dev = (char*)b.g_dev;
+  b.g_host.reserve_keep(first, 0);
+  char* dev = (char*)b.g_dev.data();
   gsd::SlotOut* d_slots = (gsd::SlotOut*)(dev + kGatherHead);
   gsd::SimOut* d_recs = (gsd::SimOut*)(dev + recs_off);
   gsd::OptPair* d_opts = (gsd::OptPair*)(dev + opts_off);
@@ -253,18 +208,18 @@ Gathered gather_all(gs_ctx* c, ConsBatch& b, gs_batch_fetch_stats& fs) {
     HIPCHK(gsk_cons_gather_batch(b.problems() + g.first, b.blocks() + g.first, b.sim_base() + g.first, g.count, g.max_sims,
                                  d_slots + g.first, d_recs, d_opts, (uint32_t*)dev, c->stream));
   HIPCHK(hipEventRecord(c->ev[7], c->stream));
-  HIPCHK(hipMemcpyAsync(b.g_host, dev, first, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(b.g_host.data(), dev, first, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   fs.n_launches = 1u + 2u * (uint32_t)b.groups.size();
   fs.n_copies = 1;
   fs.bytes = first;
   Gathered g;
-  g.n_opts = *(const uint32_t*)b.g_host;
+  g.n_opts = *(const uint32_t*)b.g_host.data();
   if (g.n_opts > b.n_sims * gsd::SIM_OPTS_MAX) throw HipError{"gs_batch_consolidate_fetch_all: corrupt option count"};
   if (g.n_opts > b.opt_hint) {
     const size_t bytes = (size_t)(g.n_opts - b.opt_hint) * sizeof(gsd::OptPair);
-    grow_host(first + bytes, first);
-    HIPCHK(hipMemcpyAsync((char*)b.g_host + first, d_opts + b.opt_hint, bytes, hipMemcpyDeviceToHost, c->stream));
+    b.g_host.reserve_keep(first + bytes, first);
+    HIPCHK(hipMemcpyAsync((char*)b.g_host.data() + first, d_opts + b.opt_hint, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     fs.n_copies++;
     fs.bytes += bytes;
@@ -273,7 +228,7 @@ Gathered gather_all(gs_ctx* c, ConsBatch& b, gs_batch_fetch_stats& fs) {
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, c->ev[6], c->ev[7]));
   fs.device_ms = ms;
-  const char* host = (const char*)b.g_host;
+  const char* host = (const char*)b.g_host.data();
   g.slots = (const gsd::SlotOut*)(host + kGatherHead);
   g.recs = (const gsd::SimOut*)(host + recs_off);
   g.opts = (const gsd::OptPair*)(host + opts_off);
@@ -291,14 +246,7 @@ bool records_valid(const Gathered& g, const gsd::SlotOut& so, const gsd::SimOut*
 }  // namespace
 
 void batch_consolidate_destroy(gs_ctx* c) {
-  ConsBatch* b = c->cons_batch;
-  if (!b) return;
-  for (auto& s : b->slots)
-    if (s.c) free_slot(s.c);
-  if (b->dev) (void)hipFree(b->dev);
-  if (b->g_dev) (void)hipFree(b->g_dev);
-  if (b->g_host) (void)hipHostFree(b->g_host);
-  delete b;
+  delete c->cons_batch;  // its slots and buffers with it
   c->cons_batch = nullptr;
 }
 
@@ -322,50 +270,30 @@ gs_status gs_batch_consolidate_prepare(gs_ctx* c, const gs_consolidation* const*
   b.groups.clear();
   b.order.clear();
   b.fstats = gs_batch_fetch_stats{};
-  while (b.slots.size() < n) {
-    ConsSlot s;
-    s.c = new gs_ctx();
-    s.c->device = c->device;
-    s.c->cfg_flags = c->cfg_flags;
-    s.c->stream = c->stream;
-    std::copy(std::begin(c->ev), std::end(c->ev), std::begin(s.c->ev));
-    b.slots.push_back(s);
-  }
+  b.ensure_slots(c, n);
   // check, take + encode and plan the sets on up to 16 host threads (the
   // encoder's own loops share its pool)
-  std::atomic<uint32_t> next{0};
-  auto work = [&] {
-    for (;;) {
-      const uint32_t i = next.fetch_add(1);
-      if (i >= n) return;
-      ConsSlot& s = b.slots[i];
-      gs_ctx* sc = s.c;
-      sc->prepared = sc->ran = false;
-      sc->cons_ready = false;
-      sc->err.clear();
-      sc->sims = SimPlan{};
-      sc->commands.clear();
-      s.grouped = s.fallback = s.fetched = false;
-      s.fetch_status = GS_OK;
-      std::string err;
-      s.status = cons_check_input(in[i], &err);
-      if (s.status != GS_OK) {
-        fail(sc, s.status, err);
-        continue;
-      }
-      s.status = cons_take_input(sc, in[i]);
-      if (s.status != GS_OK) continue;
-      s.status = cons_plan_sets(sc, &err);
-      if (s.status != GS_OK) fail(sc, s.status, err);
+  parallel_for(n, kEncodeThreads, [&](uint32_t i) {
+    ConsSlot& s = b.slots[i];
+    gs_ctx* sc = s.c;
+    sc->prepared = sc->ran = false;
+    sc->cons_ready = false;
+    sc->err.clear();
+    sc->sims = SimPlan{};
+    sc->commands.clear();
+    s.grouped = s.fallback = s.fetched = false;
+    s.fetch_status = GS_OK;
+    std::string err;
+    s.status = cons_check_input(in[i], &err);
+    if (s.status != GS_OK) {
+      fail(sc, s.status, err);
+      return;
     }
-  };
-  {
-    std::vector<std::thread> th;
-    const uint32_t nt = std::min<uint32_t>(kEncodeThreads, n);
-    for (uint32_t t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto& t : th) t.join();
-  }
+    s.status = cons_take_input(sc, in[i]);
+    if (s.status != GS_OK) return;
+    s.status = cons_plan_sets(sc, &err);
+    if (s.status != GS_OK) fail(sc, s.status, err);
+  });
   // the batch's shape from all its simulations, each slot's share of its
   // group's resident workgroups, then the uploads and the device array
   uint32_t accepted = 0;
@@ -399,10 +327,10 @@ gs_status gs_batch_consolidate_prepare(gs_ctx* c, const gs_consolidation* const*
     b.n = n;
     build_groups(c, b);
   } catch (const HipError& e) {
-    for (uint32_t i = 0; i < n; i++) status[i] = b.slots[i].status;
+    b.copy_status(status, n);
     return fail(c, GS_E_HIP, e.msg);
   }
-  for (uint32_t i = 0; i < n; i++) status[i] = b.slots[i].status;
+  b.copy_status(status, n);
   b.prepared = true;
   b.stats = gs_batch_stats{};
   b.stats.n_problems = n;
@@ -517,10 +445,8 @@ gs_status gs_batch_consolidate_fetch_all(gs_ctx* c, gs_consolidation_result* out
     pos_of[b.order[p]] = p;
     pending = pending || !b.slots[b.order[p]].fetched;
   }
-  for (uint32_t i = 0; i < b.n; i++) {
-    status[i] = b.slots[i].status;
-    std::memset(&out[i], 0, sizeof(out[i]));
-  }
+  b.copy_status(status, b.n);
+  if (b.n) std::memset(out, 0, (size_t)b.n * sizeof(*out));
   Gathered g;
   bool gathered = false;
   if (pending && b.n_sims <= kGatherMaxSims) {
@@ -572,22 +498,17 @@ gs_status gs_batch_consolidate_fetch_all(gs_ctx* c, gs_consolidation_result* out
 }
 
 gs_status gs_batch_consolidate_last_fetch(const gs_ctx* c, gs_batch_fetch_stats* out) {
-  if (!c || !out || !c->cons_batch || !c->cons_batch->prepared) return GS_E_INVALID;
-  *out = c->cons_batch->fstats;
-  return GS_OK;
+  return batch_last_fetch(c ? c->cons_batch : nullptr, out);
 }
 
 uint32_t gs_batch_fetch_stats_size(void) { return (uint32_t)sizeof(gs_batch_fetch_stats); }
 
 size_t gs_batch_consolidate_error(const gs_ctx* c, uint32_t i, char* buf, size_t len) {
-  if (!c || !c->cons_batch || i >= c->cons_batch->n) return 0;
-  return gs_last_error(c->cons_batch->slots[i].c, buf, len);
+  return batch_error(c ? c->cons_batch : nullptr, i, buf, len);
 }
 
 gs_status gs_batch_consolidate_last_run(const gs_ctx* c, gs_batch_stats* out) {
-  if (!c || !out || !c->cons_batch || !c->cons_batch->prepared) return GS_E_INVALID;
-  *out = c->cons_batch->stats;
-  return GS_OK;
+  return batch_last_run(c ? c->cons_batch : nullptr, out);
 }
 
 }  // extern "C"

@@ -331,15 +331,14 @@ void build_grid_orders(gs_ctx* c) {
   }
   const size_t bl = list.size() * 8, bo = off.size() * 4, bk = keys.size() * 8, bi = its.size() * 4,
                bp = planes.size() * 8, bb = blocks.size() * 8;
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   char* p = nullptr;
-  HIPCHK(hipMalloc((void**)&p, up(bl) + up(bo) + up(bk) + up(bi) + up(bp) + up(bb)));
+  HIPCHK(hipMalloc((void**)&p, up256(bl) + up256(bo) + up256(bk) + up256(bi) + up256(bp) + up256(bb)));
   c->allocs.push_back(p);
-  char* po = p + up(bl);
-  char* pk = po + up(bo);
-  char* pi = pk + up(bk);
-  char* pp = pi + up(bi);
-  char* pb = pp + up(bp);
+  char* po = p + up256(bl);
+  char* pk = po + up256(bo);
+  char* pi = pk + up256(bk);
+  char* pp = pi + up256(bi);
+  char* pb = pp + up256(bp);
   HIPCHK(hipMemcpyAsync(p, list.data(), bl, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(po, off.data(), bo, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(pk, keys.data(), bk, hipMemcpyHostToDevice, c->stream));
@@ -649,16 +648,17 @@ void gs_destroy(gs_ctx* c) {
   (void)hipSetDevice(c->device);
   batch_destroy(c);
   batch_consolidate_destroy(c);
-  c->free_all();
-  if (c->arena) (void)hipFree(c->arena);
-  if (c->stage) (void)hipHostFree(c->stage);
   create_filter_destroy(c);
   rank_batch_destroy(c);
   explain_destroy(c);
-  for (auto& e : c->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
+  // the context's own memory (~gs_ctx), then the stream and the events
+  const hipStream_t stream = c->stream;
+  hipEvent_t ev[8];
+  std::copy(std::begin(c->ev), std::end(c->ev), ev);
   delete c;
+  for (auto& e : ev)
+    if (e) (void)hipEventDestroy(e);
+  if (stream) (void)hipStreamDestroy(stream);
 }
 
 gs_status gs_prepare(gs_ctx* c, const gs_problem* p) {

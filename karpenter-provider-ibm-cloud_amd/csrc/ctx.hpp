@@ -18,6 +18,7 @@
 
 #include "../../include/gpusched.h"
 #include "encode.hpp"
+#include "growbuf.hpp"
 #include "layout.hpp"
 
 extern "C" hipError_t gsk_init_trunc(uint32_t trunc_lds_bytes);
@@ -88,6 +89,27 @@ struct HipError {
     hipError_t e_ = (x);                                                                 \
     if (e_ != hipSuccess) throw HipError{std::string(#x) + ": " + hipGetErrorString(e_)}; \
   } while (0)
+
+// the library's two kinds of grow-only buffer (growbuf.hpp): device memory and
+// pinned host memory.  A member of one of these types is freed with its owner.
+struct DevMem {
+  static void* alloc(size_t bytes) {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, bytes));
+    return p;
+  }
+  static void free(void* p) { HIPCHK(hipFree(p)); }
+};
+struct PinnedMem {
+  static void* alloc(size_t bytes) {
+    void* p = nullptr;
+    HIPCHK(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+    return p;
+  }
+  static void free(void* p) { HIPCHK(hipHostFree(p)); }
+};
+using DevBuf = GrowBuf<DevMem>;
+using PinnedBuf = GrowBuf<PinnedMem>;
 
 // one disruption candidate: <U> Candidate.instanceType / capacityType and
 // getCandidatePrices' c.instanceType.Offerings.Compatible(labels).Cheapest()
@@ -241,10 +263,11 @@ struct gs_ctx {
   size_t plan_bytes = 0;
   size_t ov_hn_bytes = 0;  // the simulation overlay cells (cleared when the stamp prefix wraps)
   size_t hc_bytes = 0;     // simulations: the NodeClaim hostname-count rows (zero at rest)
-  void* arena = nullptr;
-  size_t arena_bytes = 0;
-  void* stage = nullptr;  // pinned
-  size_t stage_bytes = 0;
+  gsc::DevBuf arena;
+  gsc::PinnedBuf stage;
+  // memory only (with the two members above): a batch slot borrows its
+  // parent's stream and events, which gs_destroy destroys for their owner
+  ~gs_ctx() { free_all(); }
   template <class P>
   void alloc(P*& dst, size_t n) {
     const size_t b = std::max<size_t>(n, 1) * sizeof(P);
@@ -346,51 +369,36 @@ void next_overlay_epoch(gs_ctx* c);
 
 inline void gs_ctx::commit() {
   using gsc::HipError;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   // uploaded buffers first (one contiguous image), then zeroed, then the rest
   size_t off_up = 0, off_zero = 0, off_rest = 0;
   for (auto& q : plan)
-    if (q.src) off_up += up(q.bytes);
-    else if (q.zero) off_zero += up(q.bytes);
-    else off_rest += up(q.bytes);
+    if (q.src) off_up += gsc::up256(q.bytes);
+    else if (q.zero) off_zero += gsc::up256(q.bytes);
+    else off_rest += gsc::up256(q.bytes);
   const size_t n_up = off_up, n_zero = off_zero, total = std::max<size_t>(n_up + n_zero + off_rest, 256);
-  if (total > arena_bytes) {
-    if (arena) HIPCHK(hipFree(arena));
-    arena = nullptr;
-    arena_bytes = 0;
-    const size_t want = total + total / 4;  // headroom: a slightly larger problem reuses it
-    HIPCHK(hipMalloc(&arena, want));
-    arena_bytes = want;
-  }
-  if (n_up > stage_bytes) {
-    if (stage) HIPCHK(hipHostFree(stage));
-    stage = nullptr;
-    stage_bytes = 0;
-    const size_t want = n_up + n_up / 4;
-    HIPCHK(hipHostMalloc(&stage, want, hipHostMallocDefault));
-    stage_bytes = want;
-  }
-  char* base = (char*)arena;
+  arena.reserve(total);  // with headroom: a slightly larger problem reuses it
+  stage.reserve(n_up);
+  char* base = (char*)arena.data();
   std::vector<gsh::HostCopy> copies;
   size_t a = 0, z = n_up, r = n_up + n_zero;
   for (auto& q : plan) {
     if (q.src) {
       *q.dst = base + a;
       copies.push_back({q.src, a, q.bytes});
-      a += up(q.bytes);
+      a += gsc::up256(q.bytes);
     } else if (q.zero) {
       *q.dst = base + z;
-      z += up(q.bytes);
+      z += gsc::up256(q.bytes);
     } else {
       *q.dst = base + r;
-      r += up(q.bytes);
+      r += gsc::up256(q.bytes);
     }
   }
   const auto t0 = gsc::Clock::now();
-  gsh::host_copy_parallel(stage, copies.data(), copies.size());
+  gsh::host_copy_parallel(stage.data(), copies.data(), copies.size());
   t_stage_ms = gsc::ms_since(t0);
   const auto t1 = gsc::Clock::now();
-  if (n_up) HIPCHK(hipMemcpyAsync(base, stage, n_up, hipMemcpyHostToDevice, stream));
+  if (n_up) HIPCHK(hipMemcpyAsync(base, stage.data(), n_up, hipMemcpyHostToDevice, stream));
   if (n_zero) HIPCHK(hipMemsetAsync(base + n_up, 0, n_zero, stream));
   HIPCHK(hipStreamSynchronize(stream));
   t_h2d_ms = gsc::ms_since(t1);

@@ -185,28 +185,12 @@ static hipError_t launch(const DevProblem& d, const ExplainArgs& a, hipStream_t 
 // the call's device buffers and pinned staging (they only grow) and the
 // result storage the caller's gs_explain_result points into
 struct State {
-  void* dev = nullptr;
-  size_t dev_bytes = 0;
-  void* h_in = nullptr;
-  size_t h_in_bytes = 0;
-  void* h_out = nullptr;
-  size_t h_out_bytes = 0;
+  gsc::DevBuf dev;
+  gsc::PinnedBuf h_in, h_out;
   std::vector<uint32_t> pods;
   std::vector<uint8_t> cause, met;
   std::vector<int32_t> taint;
 };
-
-static void grow_pinned(void*& p, size_t& cap, size_t want) {
-  using gsc::HipError;
-  if (want <= cap) return;
-  if (p) HIPCHK(hipHostFree(p));
-  p = nullptr;
-  cap = 0;
-  HIPCHK(hipHostMalloc(&p, want + want / 4, hipHostMallocDefault));
-  cap = want + want / 4;
-}
-
-static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace gse
 
@@ -214,12 +198,7 @@ using namespace gsc;
 using namespace gse;
 
 void gsc::explain_destroy(gs_ctx* c) {
-  State* s = c->explain;
-  if (!s) return;
-  if (s->dev) (void)hipFree(s->dev);
-  if (s->h_in) (void)hipHostFree(s->h_in);
-  if (s->h_out) (void)hipHostFree(s->h_out);
-  delete s;
+  delete c->explain;  // its buffers with it
   c->explain = nullptr;
 }
 
@@ -306,20 +285,14 @@ extern "C" gs_status gs_explain(gs_ctx* c, const uint32_t* pods, uint32_t n, uin
       HIPCHK(hipSetDevice(c->device));
       if (!c->explain) c->explain = new State;
       State& s = *c->explain;
-      if (total > s.dev_bytes) {
-        if (s.dev) HIPCHK(hipFree(s.dev));
-        s.dev = nullptr;
-        s.dev_bytes = 0;
-        HIPCHK(hipMalloc(&s.dev, total + total / 4));
-        s.dev_bytes = total + total / 4;
-      }
-      grow_pinned(s.h_in, s.h_in_bytes, in_bytes);
-      grow_pinned(s.h_out, s.h_out_bytes, out_bytes);
-      char* hi = (char*)s.h_in;
+      s.dev.reserve(total);
+      s.h_in.reserve(in_bytes);
+      s.h_out.reserve(out_bytes);
+      char* hi = (char*)s.h_in.data();
       std::memcpy(hi, ev.data(), ev_b);
       std::memcpy(hi + inc_off, inc.data(), inc_b);
       std::memcpy(hi + tc_off, tcls.data(), tc_b);
-      char* base = (char*)s.dev;
+      char* base = (char*)s.dev.data();
       HIPCHK(hipMemcpyAsync(base, hi, in_bytes, hipMemcpyHostToDevice, c->stream));
       ExplainArgs a{};
       a.ev = (const uint32_t*)base;
@@ -331,7 +304,7 @@ extern "C" gs_status gs_explain(gs_ctx* c, const uint32_t* pods, uint32_t n, uin
       HIPCHK(hipEventRecord(c->ev[6], c->stream));
       HIPCHK(launch(c->dp, a, c->stream));
       HIPCHK(hipEventRecord(c->ev[7], c->stream));
-      HIPCHK(hipMemcpyAsync(s.h_out, base + out_off, out_bytes, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipMemcpyAsync(s.h_out.data(), base + out_off, out_bytes, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(hipStreamSynchronize(c->stream));
       HIPCHK(hipEventElapsedTime(&kernel_ms, c->ev[6], c->ev[7]));
       d2h = out_bytes;
@@ -339,7 +312,7 @@ extern "C" gs_status gs_explain(gs_ctx* c, const uint32_t* pods, uint32_t n, uin
       return fail(c, GS_E_HIP, ex.msg);
     }
     // the evaluated pairs -> the requested pods' rows
-    const uint32_t* words = (const uint32_t*)c->explain->h_out;
+    const uint32_t* words = (const uint32_t*)c->explain->h_out.data();
     for (size_t q = 0; q < pairs; q++)
       if (gsx::packed_cause(words[q]) >= gsx::WHY_COUNT || gsx::packed_cause(words[q]) == gsx::WHY_NO_OPTIONS)
         return fail(c, GS_E_HIP, "gs_explain: a cause code outside the table came back");

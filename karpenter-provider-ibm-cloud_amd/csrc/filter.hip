@@ -170,15 +170,11 @@ struct Resident {
   uint32_t N = 0, W = 0;
   std::vector<FOff> offs;                    // host mirror of the device array
   std::vector<std::vector<uint32_t>> slots;  // catalog offering index -> positions in offs
-  void* cat_dev = nullptr;                   // the catalog image
+  gsc::DevBuf cat_dev;                       // the catalog image
   CatalogImage cat;
   // a run's claim image and outputs: grow-once device arena, pinned host sides
-  void* run_dev = nullptr;
-  size_t run_bytes = 0;
-  void* h_in = nullptr;
-  size_t h_in_bytes = 0;
-  void* h_out = nullptr;
-  size_t h_out_bytes = 0;
+  gsc::DevBuf run_dev;
+  gsc::PinnedBuf h_in, h_out;
   std::vector<uint32_t> res_n, res_ct;
   std::vector<int32_t> res_sel;
   gs_create_filter_stats stats{};
@@ -187,8 +183,7 @@ struct Resident {
 // everything the re-filter keeps in a context (gs_ctx::cf, made on first use)
 struct State {
   // gs_create_filter: grow-once device arena and result storage
-  void* dev = nullptr;
-  size_t bytes = 0;
+  gsc::DevBuf dev;
   std::vector<uint64_t> create, reqs, spot;
   std::vector<uint32_t> n, ct;
   std::vector<int32_t> sel;
@@ -206,24 +201,8 @@ static State& state(gs_ctx* c) {
   return *c->cf;
 }
 
-static void grow_pinned(void*& p, size_t& cap, size_t want) {
-  if (want <= cap) return;
-  if (p) HIPCHK(hipHostFree(p));
-  p = nullptr;
-  cap = 0;
-  HIPCHK(hipHostMalloc(&p, want + want / 4, hipHostMallocDefault));
-  cap = want + want / 4;
-}
-
 void gsc::create_filter_destroy(gs_ctx* c) {
-  State* s = c->cf;
-  if (!s) return;
-  if (s->dev) (void)hipFree(s->dev);
-  if (s->res.cat_dev) (void)hipFree(s->res.cat_dev);
-  if (s->res.run_dev) (void)hipFree(s->res.run_dev);
-  if (s->res.h_in) (void)hipHostFree(s->res.h_in);
-  if (s->res.h_out) (void)hipHostFree(s->res.h_out);
-  delete s;
+  delete c->cf;  // its buffers with it
   c->cf = nullptr;
 }
 
@@ -266,14 +245,8 @@ extern "C" gs_status gs_create_filter(gs_ctx* c, const gs_problem* p, const gs_c
       const CatalogImage cat(im, e, its, offs, alloc);
       const ClaimImage claims(im, nullptr, fq, qty);
       const size_t o_out = im.place((size_t)3 * nq * W * 8);
-      if (im.off > s.bytes) {
-        if (s.dev) HIPCHK(hipFree(s.dev));
-        s.dev = nullptr;
-        s.bytes = 0;
-        HIPCHK(hipMalloc(&s.dev, im.off));
-        s.bytes = im.off;
-      }
-      char* base = (char*)s.dev;
+      s.dev.reserve_exact(im.off);
+      char* base = (char*)s.dev.data();
       // staging: one host copy, one H2D transfer
       std::vector<char> h(o_out);
       cat.fill(h.data(), e, its, offs, alloc);
@@ -364,19 +337,17 @@ extern "C" gs_status gs_create_filter_prepare(gs_ctx* c, const gs_problem* p) {
   cat.fill(h.data(), e, its, offs, alloc);
   const double encode_ms = ms_since(t0);
   const auto t1 = Clock::now();
-  void* dev = nullptr;
+  DevBuf dev;  // the new image: freed by scope on a failure
   try {
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMalloc(&dev, im.off));
-    HIPCHK(hipMemcpyAsync(dev, h.data(), im.off, hipMemcpyHostToDevice, c->stream));
+    dev.reserve_exact(im.off);
+    HIPCHK(hipMemcpyAsync(dev.data(), h.data(), im.off, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));  // also: no run of the old catalog is in flight
   } catch (const HipError& ex) {
-    if (dev) (void)hipFree(dev);
     return fail(c, GS_E_HIP, ex.msg);
   }
   Resident& r = state(c).res;
-  if (r.cat_dev) (void)hipFree(r.cat_dev);
-  r.cat_dev = dev;
+  r.cat_dev = std::move(dev);  // frees the old image
   // keep the vocabularies; the lists live on the device now
   e.p = nullptr;
   e.reqs = {};
@@ -415,7 +386,7 @@ extern "C" gs_status gs_create_filter_set_available(gs_ctx* c, const uint32_t* o
     HIPCHK(hipSetDevice(c->device));
     // the whole FOff array (16 B per offering) from the patched mirror: one
     // transfer whatever n is, on the stream the next run is launched on
-    HIPCHK(hipMemcpyAsync((char*)r->cat_dev + r->cat.offs, r->offs.data(), r->offs.size() * sizeof(FOff),
+    HIPCHK(hipMemcpyAsync((char*)r->cat_dev.data() + r->cat.offs, r->offs.data(), r->offs.size() * sizeof(FOff),
                           hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));  // the mirror may change again after this call
   } catch (const HipError& ex) {
@@ -471,24 +442,17 @@ extern "C" gs_status gs_create_filter_run(gs_ctx* c, const gs_problem* p, const 
       const size_t in_bytes = im.off;
       const size_t bs_bytes = bits ? (size_t)nq * W * 8 : 0;
       const size_t out_bytes = (size_t)nq * sizeof(FRec) + 2 * bs_bytes;
-      if (in_bytes + out_bytes > r.run_bytes) {
-        if (r.run_dev) HIPCHK(hipFree(r.run_dev));
-        r.run_dev = nullptr;
-        r.run_bytes = 0;
-        const size_t want = in_bytes + out_bytes + (in_bytes + out_bytes) / 4;
-        HIPCHK(hipMalloc(&r.run_dev, want));
-        r.run_bytes = want;
-      }
-      grow_pinned(r.h_in, r.h_in_bytes, in_bytes);
-      grow_pinned(r.h_out, r.h_out_bytes, out_bytes);
-      claims.fill((char*)r.h_in, &e, fq, qty);
+      r.run_dev.reserve(in_bytes + out_bytes);
+      r.h_in.reserve(in_bytes);
+      r.h_out.reserve(out_bytes);
+      claims.fill((char*)r.h_in.data(), &e, fq, qty);
       st.encode_ms = ms_since(t0);
       const auto t1 = Clock::now();
-      char* base = (char*)r.run_dev;
-      HIPCHK(hipMemcpyAsync(base, r.h_in, in_bytes, hipMemcpyHostToDevice, c->stream));
+      char* base = (char*)r.run_dev.data();
+      HIPCHK(hipMemcpyAsync(base, r.h_in.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
       st.h2d_bytes = in_bytes;
       DevSelect d{};
-      r.cat.bind((const char*)r.cat_dev, d);
+      r.cat.bind((const char*)r.cat_dev.data(), d);
       claims.bind(base, d);
       claims.bind_lists(base, d);
       d.N = r.N;
@@ -507,20 +471,20 @@ extern "C" gs_status gs_create_filter_run(gs_ctx* c, const gs_problem* p, const 
       st.n_launches = 1;
       st.upload_ms = ms_since(t1);
       const auto t2 = Clock::now();
-      HIPCHK(hipMemcpyAsync(r.h_out, base + in_bytes, out_bytes, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipMemcpyAsync(r.h_out.data(), base + in_bytes, out_bytes, hipMemcpyDeviceToHost, c->stream));
       st.d2h_bytes = out_bytes;
       HIPCHK(hipStreamSynchronize(c->stream));
       float ms = 0;
       HIPCHK(hipEventElapsedTime(&ms, c->ev[6], c->ev[7]));
       st.kernel_ms = ms;
-      const FRec* rec = (const FRec*)r.h_out;
+      const FRec* rec = (const FRec*)r.h_out.data();
       for (uint32_t q = 0; q < nq; q++) {
         r.res_n[q] = rec[q].n_compatible;
         r.res_sel[q] = rec[q].selected;
         r.res_ct[q] = rec[q].capacity_type;
       }
       if (bits) {
-        h_create = (const uint64_t*)((const char*)r.h_out + (size_t)nq * sizeof(FRec));
+        h_create = (const uint64_t*)((const char*)r.h_out.data() + (size_t)nq * sizeof(FRec));
         h_reqs = h_create + (size_t)nq * W;
       }
       st.fetch_ms = ms_since(t2);

@@ -139,15 +139,11 @@ __global__ __launch_bounds__(64) void rank_batch_kernel(DevCatalog d, DevRun r) 
 // everything the resident ranking keeps in a context (gs_ctx::rank, made on first use)
 struct State {
   bool ready = false;
-  void* cat_dev = nullptr;
+  gsc::DevBuf cat_dev;
   DevCatalog cat{};
   // a run's queries and outputs: grow-once device arena, pinned host sides
-  void* run_dev = nullptr;
-  size_t run_bytes = 0;
-  void* h_in = nullptr;
-  size_t h_in_bytes = 0;
-  void* h_out = nullptr;
-  size_t h_out_bytes = 0;
+  gsc::DevBuf run_dev;
+  gsc::PinnedBuf h_in, h_out;
   gs_rank_stats stats{};
 };
 
@@ -156,30 +152,13 @@ static State& state(gs_ctx* c) {
   return *c->rank;
 }
 
-static void grow_pinned(void*& p, size_t& cap, size_t want) {
-  if (want <= cap) return;
-  if (p) HIPCHK(hipHostFree(p));
-  p = nullptr;
-  cap = 0;
-  HIPCHK(hipHostMalloc(&p, want + want / 4, hipHostMallocDefault));
-  cap = want + want / 4;
-}
-
-static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace gsrb
 
 using namespace gsc;
 using namespace gsrb;
 
 void gsc::rank_batch_destroy(gs_ctx* c) {
-  State* s = c->rank;
-  if (!s) return;
-  if (s->cat_dev) (void)hipFree(s->cat_dev);
-  if (s->run_dev) (void)hipFree(s->run_dev);
-  if (s->h_in) (void)hipHostFree(s->h_in);
-  if (s->h_out) (void)hipHostFree(s->h_out);
-  delete s;
+  delete c->rank;  // its buffers with it
   c->rank = nullptr;
 }
 
@@ -219,12 +198,13 @@ extern "C" gs_status gs_rank_prepare(gs_ctx* c, uint32_t n, const int64_t* cpu_m
   }
   const double encode_ms = ms_since(t0);
   const auto t1 = Clock::now();
-  char* dev = nullptr;
+  DevBuf image;  // the new catalog: freed by scope on a failure
   DevCatalog d{};
   float kernel_ms = 0;
   try {
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMalloc((void**)&dev, bytes));
+    image.reserve_exact(bytes);
+    char* dev = (char*)image.data();
     d.cpu_milli = (const int64_t*)dev;
     d.memory_bytes = (const int64_t*)(dev + nn * 8);
     d.price = (const double*)(dev + nn * 16);
@@ -242,12 +222,10 @@ extern "C" gs_status gs_rank_prepare(gs_ctx* c, uint32_t n, const int64_t* cpu_m
     HIPCHK(hipStreamSynchronize(c->stream));  // also: no run of the old catalog is in flight
     if (n) HIPCHK(hipEventElapsedTime(&kernel_ms, c->ev[6], c->ev[7]));
   } catch (const HipError& ex) {
-    if (dev) (void)hipFree(dev);
     return fail(c, GS_E_HIP, ex.msg);
   }
   State& s = state(c);
-  if (s.cat_dev) (void)hipFree(s.cat_dev);
-  s.cat_dev = dev;
+  s.cat_dev = std::move(image);  // frees the old catalog
   s.cat = d;
   s.ready = true;
   s.stats = gs_rank_stats{};
@@ -287,21 +265,14 @@ extern "C" gs_status gs_rank_run(gs_ctx* c, const gs_rank_query* q, uint32_t nq,
       const size_t score_bytes = scores ? cells * 8 : 0;
       const size_t out_bytes = score_bytes + cells * 4 + (size_t)nq * 4;  // scores | order | kept
       const size_t out_off = up256(in_bytes);
-      if (out_off + out_bytes > s.run_bytes) {
-        if (s.run_dev) HIPCHK(hipFree(s.run_dev));
-        s.run_dev = nullptr;
-        s.run_bytes = 0;
-        const size_t want = out_off + out_bytes + (out_off + out_bytes) / 4;
-        HIPCHK(hipMalloc(&s.run_dev, want));
-        s.run_bytes = want;
-      }
-      grow_pinned(s.h_in, s.h_in_bytes, in_bytes);
-      grow_pinned(s.h_out, s.h_out_bytes, out_bytes);
-      std::memcpy(s.h_in, q, in_bytes);
+      s.run_dev.reserve(out_off + out_bytes);
+      s.h_in.reserve(in_bytes);
+      s.h_out.reserve(out_bytes);
+      std::memcpy(s.h_in.data(), q, in_bytes);
       st.encode_ms = ms_since(t0);
       const auto t1 = Clock::now();
-      char* base = (char*)s.run_dev;
-      HIPCHK(hipMemcpyAsync(base, s.h_in, in_bytes, hipMemcpyHostToDevice, c->stream));
+      char* base = (char*)s.run_dev.data();
+      HIPCHK(hipMemcpyAsync(base, s.h_in.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
       st.h2d_bytes = in_bytes;
       DevRun r{};
       r.q = (const gs_rank_query*)base;
@@ -317,13 +288,13 @@ extern "C" gs_status gs_rank_run(gs_ctx* c, const gs_rank_query* q, uint32_t nq,
       st.n_launches = 1;
       st.upload_ms = ms_since(t1);
       const auto t2 = Clock::now();
-      HIPCHK(hipMemcpyAsync(s.h_out, base + out_off, out_bytes, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipMemcpyAsync(s.h_out.data(), base + out_off, out_bytes, hipMemcpyDeviceToHost, c->stream));
       st.d2h_bytes = out_bytes;
       HIPCHK(hipStreamSynchronize(c->stream));
       float ms = 0;
       HIPCHK(hipEventElapsedTime(&ms, c->ev[6], c->ev[7]));
       st.kernel_ms = ms;
-      const char* ho = (const char*)s.h_out;
+      const char* ho = (const char*)s.h_out.data();
       h_score = scores ? (const double*)ho : nullptr;
       h_order = (const uint32_t*)(ho + score_bytes);
       h_kept = h_order + cells;

@@ -257,6 +257,8 @@ def test_gpu_prepared_call_local_ids_do_not_persist(solver):
     a2 = solver.create_filter_run(p)
     assert a1 == want and a2 == a1
     assert solver.create_filter_last_run()["h2d_bytes"] == h1
+    # ... nor does anything of a larger run, whose buffers regrow, or of a re-prepare
+    _check_buffers_regrow_and_shrink()
 
 
 @pytest.mark.gpu
@@ -377,3 +379,44 @@ def test_gpu_prepared_after_solve(solver, seed):
     p2 = p.extended(lambda b: claim_queries_from_solve(p, res, b))
     solver.create_filter_prepare(p2)
     assert solver.create_filter_run(p2) == pyoracle.create_filter(p2)[1]
+
+
+def _check_buffers_regrow_and_shrink():
+    """One context: 1 claim, then 40 (the run's device buffer and both pinned
+    sides regrow), then the 1 again; the same after a re-prepare, whose answers
+    follow the new catalog; and gs_create_filter's own arena through the same
+    sequence.  Each answer is a fresh context's for the same input."""
+    cats = (case(108, 257, 40)[0], case(102, 63, 30)[0])
+    claims = claims_of(cats[0])
+    assert len(claims) == 40
+    one = claims[2:3]  # a claim that keeps many types of either catalog
+    pools = (pool_of(one), pool_of(claims))
+    whole = [random_catalog(108, 257, 0).extended(lambda b, cs=cs: [b.add_claim_query(r, q) for r, q in cs])
+             for cs in (one, claims)]
+
+    def fresh(fn):
+        s = lib.Solver()
+        try:
+            return fn(s)
+        finally:
+            s.close()
+
+    def prepared_run(s, cat, pool):
+        s.create_filter_prepare(cat)
+        return s.create_filter_run(pool)
+
+    want = [[fresh(lambda s, cat=cat, pool=pool: prepared_run(s, cat, pool)) for pool in pools] for cat in cats]
+    assert want[0][1] == case(108, 257, 40)[1] and want[0][0] == want[0][1][2:3]  # ... which is the oracle's
+    assert want[0][0][0]["n_compatible"] > want[1][0][0]["n_compatible"] > 0 and want[1][1] != want[0][1]
+    want_whole = [fresh(lambda s, p=p: s.create_filter(p)) for p in whole]
+    assert want_whole[1] == want[0][1]
+    s = lib.Solver()
+    try:
+        for cat, w in zip(cats, want):
+            s.create_filter_prepare(cat)
+            for j in (0, 1, 0):
+                assert s.create_filter_run(pools[j]) == w[j], j
+        for j in (0, 1, 0):
+            assert s.create_filter(whole[j]) == want_whole[j], j
+    finally:
+        s.close()

@@ -655,6 +655,8 @@ def test_call_forms(solver):
     again = abi.GsExplainResult()
     assert solver.L.gs_explain(solver.ctx, keep.pods, keep.n_pods, 0, C.byref(again)) == abi.GS_OK
     _same(abi.explain_to_dict(again), before, "own list")
+    # a short list, every pod, the short list again: the buffers regrow and are reused
+    _check_buffers_regrow_and_shrink()
 
 
 @pytest.mark.gpu
@@ -682,6 +684,45 @@ def test_relaxation(solver):
     assert solver.explain()["cause"][p, 0] == W.GS_WHY_IT_RESOURCES
     assert solver.explain(as_given=True)["cause"][p, 0] == W.GS_WHY_IT_FITS_OR_OFFERING
     _same(solver.explain(as_given=True), Model(pr).explain(as_given=True), "as given")
+
+
+def _check_buffers_regrow_and_shrink():
+    """One context: 2 pods, then all 64 (2 -> 64 variants: the device buffer and
+    both pinned sides regrow), then the 2 again.  Each answer is a fresh
+    context's for the same call, and the model's."""
+    b = ProblemBuilder()
+    kat_catalog(b)
+    b.add_nodepool("open")
+    b.add_nodepool("tainted", taints=[("dedicated", "x", "NoSchedule")])
+    for i in range(64):
+        kw = {"required_terms": [[(ARCH, "In", ["ppc64le"])]]} if i % 7 == 3 else {}
+        _pod(b, HUGE if i % 5 == 2 else {"cpu": 500 + 10 * i, "memory": GI * 1000, "pods": 1000},
+             tolerations=TOL_ALL if i % 3 == 0 else [], **kw)
+    pr = b.build()
+    calls = ([5, 2], None)
+
+    def fresh(pods):
+        s = lib.Solver(0)
+        try:
+            s.prepare(pr)
+            return s.explain(pods=pods)
+        finally:
+            s.close()
+
+    want = [fresh(pods) for pods in calls]
+    assert want[0]["n_variants"] == 2 and want[1]["n_variants"] == 64
+    assert len({tuple(want[1]["cause"][p]) for p in calls[0]}) == 2  # a stale row would show
+    s = lib.Solver(0)
+    try:
+        s.prepare(pr)
+        for j in (0, 1, 0):
+            got = s.explain(pods=calls[j])
+            assert got["pods"].tolist() == want[j]["pods"].tolist() and got["n_variants"] == want[j]["n_variants"]
+            _same(got, want[j], ("call", j))
+    finally:
+        s.close()
+    _same(want[1], Model(pr).explain(), "model")
+    _same(want[0], Model(pr).explain(pods=calls[0]), "model, two pods")
 
 
 def _solve_problem():

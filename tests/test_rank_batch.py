@@ -313,6 +313,8 @@ def test_gpu_rank_batch_refused_prepare_keeps_the_catalog(solver):
     solver.rank_prepare(*cols2)
     after = solver.rank_run(qs, scores=True)
     assert [(o, _u64(s)) for o, s in zip(after[0], after[1])] == want2
+    # ... also between runs whose buffers regrow and are reused
+    _check_buffers_regrow_and_shrink()
 
 
 @pytest.mark.gpu
@@ -370,3 +372,33 @@ def test_gpu_rank_batch_shape_of_a_run(solver):
                 assert st["h2d_bytes"] == nq * C.sizeof(abi.GsRankQuery)
                 assert st["d2h_bytes"] == nq * (4 + per * stride)
                 assert st["n_queries"] == nq and st["n_instance_types"] == n
+
+
+def _check_buffers_regrow_and_shrink():
+    """One context, a 70-type catalog (one past a wave): 1 query, then 40 (the
+    run's device buffer and both pinned sides regrow), then the 1 again; the
+    same after a re-prepare, whose answers follow the new catalog.  Each answer
+    is a fresh context's for the same input."""
+    cats = (_cat(25, 70), _cat(26, 70))
+    calls = ([dict(min_cpu=4)], [dict(min_cpu=(j % 5) * 2, want_arch=j % 2) for j in range(40)])
+
+    def fresh(cols, qs):
+        s = lib.Solver()
+        try:
+            s.rank_prepare(*cols)
+            return s.rank_run(qs, scores=True)
+        finally:
+            s.close()
+
+    want = [[fresh(cols, qs) for qs in calls] for cols in cats]
+    for w, cols in zip(want, cats):  # ... which is the oracle's
+        assert w[0][0] == [_want(cols, calls[0][0])[0]] and [len(o) for o in w[1][0]] == w[1][2]
+    assert want[0][0] != want[1][0] and want[0][1] != want[1][1]
+    s = lib.Solver()
+    try:
+        for cols, w in zip(cats, want):
+            s.rank_prepare(*cols)
+            for j in (0, 1, 0):
+                assert s.rank_run(calls[j], scores=True) == w[j], j
+    finally:
+        s.close()
