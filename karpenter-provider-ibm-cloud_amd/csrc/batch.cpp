@@ -35,11 +35,6 @@
 #include "batch_common.hpp"
 #include "batch_fetch_layout.hpp"
 
-extern "C" uint32_t gsk_ffdw_wide(uint32_t W);
-// batch_fetch.hip: the records of n problems of a device array, packed into `staging`
-extern "C" hipError_t gsk_fetch_gather_batch(const gsd::DevProblem* ds, uint32_t n, uint32_t max_pods, void* staging,
-                                             uint64_t payload_cap, hipStream_t s);
-
 namespace gsc {
 
 using BatchSlot = SlotCore;  // fallback: solved through gs_run
@@ -66,17 +61,11 @@ namespace {
 
 constexpr uint32_t kLaunchesPerGroup = 5;
 
-// the dynamic LDS gsk_ffdw requests for a problem with its claim state in LDS
-uint32_t wave_lds(const gsd::DevProblem& d) {
-  return gsk_ffd_lds_bytes(d.max_claims_wave, d.n_thr, 0, gsd::topo_lds_bytes(d.TGZ, d.ZS, d.TGH, d.n_lazy)) +
-         gsd::wave_node_lds_bytes(d.NN);
-}
-
 bool eligible(const gs_ctx* parent, const BatchSlot& s) {
   if (s.status != GS_OK || s.fallback) return false;
   if (parent->cfg_flags & (GS_CFG_BLOCK_SOLVE | GS_CFG_CLAIMS_HBM)) return false;
   const gs_ctx* c = s.c;
-  return c->wave && !c->ch && c->dp.R >= 1 && c->dp.R <= 8 && wave_lds(c->dp) <= gsk_ffdw_batch_dyn_lds_max();
+  return c->wave && !c->ch && c->dp.R >= 1 && c->dp.R <= 8 && gsd::wave_lds_bytes(c->dp, false) <= gsk_ffdw_batch_dyn_lds_max();
 }
 
 void copy_to_device(gs_ctx* c, Batch& b, size_t n) {
@@ -95,8 +84,7 @@ void build_groups(gs_ctx* c, Batch& b) {
     const BatchSlot& s = b.slots[i];
     if (!eligible(c, s)) continue;
     const gsd::DevProblem& d = s.c->dp;
-    const uint32_t topo = (d.TG || d.any_mv || d.any_vol) ? 1u : 0u;
-    by[Key{d.R, topo, gsk_ffdw_wide(d.W), gsk_feas_lp(d.W)}].push_back(i);
+    by[Key{d.R, gsd::general_variant(d) ? 1u : 0u, gsd::wide_rows(d.W) ? 1u : 0u, gsk_feas_lp(d.W)}].push_back(i);
   }
   b.groups.clear();
   b.order.clear();
@@ -108,7 +96,7 @@ void build_groups(gs_ctx* c, Batch& b) {
     g.count = (uint32_t)kv.second.size();
     for (uint32_t i : kv.second) {
       const gsd::DevProblem& d = b.slots[i].c->dp;
-      g.lds = std::max(g.lds, wave_lds(d));
+      g.lds = std::max(g.lds, gsd::wave_lds_bytes(d, false));
       g.max_slots = std::max(g.max_slots, d.claim_cap);
       g.trunc_lds = std::max(g.trunc_lds, trunc_lds_bytes(d.N));
       g.max_pairs = std::max<uint64_t>(g.max_pairs, (uint64_t)d.V * d.T);
@@ -196,14 +184,7 @@ Gathered gather_all(gs_ctx* c, Batch& b, gs_batch_fetch_stats& fs) {
 // pay: its payload in the mirror)
 gs_status decode_gathered(gs_ctx* c, const gsbf::FetchHead& h, const char* pay, gs_result* out) {
   const auto& e = c->enc;
-  if (h.status == gsd::ST_CLAIMS)
-    return fail(c, GS_E_CAPACITY, "NodeClaim count exceeded the device capacity (" +
-                                      std::to_string(c->ch ? std::min<uint32_t>(c->dp.claim_cap, 65535) : c->dp.max_claims) +
-                                      " in-flight NodeClaims)");
-  if (h.status == gsd::ST_POD_COUNT)
-    return fail(c, GS_E_CAPACITY, "a NodeClaim would hold more than 65535 pods (16-bit pod count in LDS)");
-  if (h.status == gsd::ST_INTERNAL) return fail(c, GS_E_HIP, "ffd kernel reported an internal error (queue / channel bound)");
-  if (h.status != 0) return fail(c, GS_E_HIP, "ffd kernel reported an unknown status");
+  if (h.status != 0) return solve_status_error(c, h.status);
   const gsbf::FetchRegions r = gsbf::regions(h.n_log, h.n_claims, h.qlen);
   const SolveRecords rec{(const gsd::LogRec*)(pay + r.log),
                          h.n_log,
@@ -222,29 +203,7 @@ gs_status decode_gathered(gs_ctx* c, const gsbf::FetchHead& h, const char* pay, 
   c->ctrl.n_log = h.n_log;
   c->ctrl.qhead = h.qhead;
   c->ctrl.qlen = h.qlen;
-  out->checks = e.checks;
-  out->pops = h.pops;
-  out->cand_evals = h.cand_evals;
-  out->cand_full = h.cand_full;
-  out->claim_prefix = h.claim_prefix;
-  out->node_prefix = h.node_prefix;
-  // wall_clock64 runs at 100 MHz; ~0: the phase timers are not built in (-1)
-  auto phase_ms = [](uint64_t t) { return t == ~0ull ? -1.0 : (double)t * 1e-5; };
-  out->t_ffd_sort_ms = phase_ms(h.t_sort);
-  out->t_ffd_scan_ms = phase_ms(h.t_scan);
-  out->t_ffd_template_ms = phase_ms(h.t_tmpl);
-  out->sorts_fast = h.fast_sorts;
-  out->sorts_generic = h.generic_sorts;
-  out->words = e.W;
-  out->n_templates = e.T;
-  out->n_variants = e.V;
-  out->t_encode_ms = c->t_encode;
-  out->t_upload_ms = c->t_upload;
-  out->t_feas_ms = c->t_feas;
-  out->t_ffd_ms = c->t_ffd;
-  out->t_truncate_ms = c->t_trunc;
-  out->t_run_wall_ms = c->t_run_wall;
-  out->t_wall_ms = 0;
+  fill_solve_stats(c, h, out);
   return GS_OK;
 }
 

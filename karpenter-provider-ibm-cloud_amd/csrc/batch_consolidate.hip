@@ -82,19 +82,12 @@ namespace {
 using GroupKey = std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>;
 
 GroupKey key_of(const gsh::Encoded& e) {
-  const uint32_t general = (e.TG || e.any_mv || e.any_vol) ? 1u : 0u;
-  return GroupKey{e.R, general, gsk_feas_lp(e.W), e.any_mv ? 1u : 0u};
-}
-
-// the dynamic LDS gsk_ffd requests for a problem's simulations
-uint32_t sim_lds(const gsd::DevProblem& d) {
-  return gsk_ffd_lds_bytes(d.max_claims, d.n_thr, d.nb_words, gsd::topo_lds_bytes(d.TGZ, d.ZS, d.TGH, d.n_lazy)) +
-         8u * d.ovh_slots + (d.sim_lds ? 32u * d.max_claims : 0u);
+  return GroupKey{e.R, gsd::general_variant(e) ? 1u : 0u, gsk_feas_lp(e.W), e.any_mv ? 1u : 0u};
 }
 
 bool eligible(const ConsBatch& b, const ConsSlot& s) {
   const gsd::DevProblem& d = s.c->dp;
-  return d.R >= 1 && d.R <= 8 && d.sim_nt == b.nt && sim_lds(d) <= gsk_ffd_sim_batch_dyn_lds_max();
+  return d.R >= 1 && d.R <= 8 && d.sim_nt == b.nt && gsd::sim_lds_bytes(d) <= gsk_ffd_sim_batch_dyn_lds_max();
 }
 
 // the device array of the slots with simulations, ordered by group, and their
@@ -124,7 +117,7 @@ void build_groups(gs_ctx* c, ConsBatch& b) {
       ConsSlot& s = b.slots[i];
       const gsd::DevProblem& d = s.c->dp;
       const SimPlan& sp = s.c->sims;
-      g.lds = std::max(g.lds, sim_lds(d));
+      g.lds = std::max(g.lds, gsd::sim_lds_bytes(d));
       g.max_blocks = std::max(g.max_blocks, sp.blocks);
       g.max_sims = std::max(g.max_sims, d.n_sims);
       g.max_slots = std::max(g.max_slots, (uint32_t)sp.pods.size());

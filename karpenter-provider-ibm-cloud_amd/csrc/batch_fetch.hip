@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "batch_fetch_layout.hpp"
+#include "kernel_api.hpp"
 #include "layout.hpp"
 
 using namespace gsd;

@@ -15,6 +15,7 @@
 
 #include "devutil.hpp"
 #include "ffd_common.hpp"
+#include "kernel_api.hpp"
 #include "layout.hpp"
 
 using namespace gsd;
@@ -94,30 +95,24 @@ extern "C" hipError_t gsk_trunc_batch(const DevProblem* ds, uint32_t n, uint32_t
 }
 
 // ------------------------------------------------ the batched single-wave Solve
-// The instantiations live in ffd_wave_batch_r.hip, one translation unit per
-// (R, TOPO): each exports its launcher and its LDS attribute setter.
-#define GSK_DECL(n, t)                                                                                      \
-  extern "C" hipError_t gsk_ffdwb_launch_r##n##_t##t(const DevProblem* ds, uint32_t cnt, uint32_t wide, uint32_t lds, \
-                                                     hipStream_t s);                                        \
-  extern "C" hipError_t gsk_ffdwb_attr_r##n##_t##t(uint32_t lds_total, uint32_t* dyn_min);
-#define GSK_DECL2(n) GSK_DECL(n, 0) GSK_DECL(n, 1)
-GSK_DECL2(1) GSK_DECL2(2) GSK_DECL2(3) GSK_DECL2(4) GSK_DECL2(5) GSK_DECL2(6) GSK_DECL2(7) GSK_DECL2(8)
-#undef GSK_DECL2
-#undef GSK_DECL
+// The instantiations live in ffd_wave_batch_r.hip, and those of the batched
+// simulation kernel in ffd_sim_batch_r.hip, one translation unit per
+// (R, TOPO): each exports its family record (kernel_api.hpp).
+static auto& ffdwb_families() {
+#define GSK_ENTRY(r, t) GSK_RT_NAME(gsk_ffdwb, r, t)(),
+  static const GskWaveBatchFamily* const table[] = {GSK_FOR_EACH_RT(GSK_ENTRY)};
+#undef GSK_ENTRY
+  return table;
+}
+static auto& ffdsb_families() {
+#define GSK_ENTRY(r, t) GSK_RT_NAME(gsk_ffdsb, r, t)(),
+  static const GskSimBatchFamily* const table[] = {GSK_FOR_EACH_RT(GSK_ENTRY)};
+#undef GSK_ENTRY
+  return table;
+}
 static uint32_t g_ffdwb_dyn_max = 0;
 
-extern "C" hipError_t gsk_init_ffdw_batch(uint32_t lds_total) {
-  hipError_t e = hipSuccess;
-  uint32_t dmin = 0;
-#define GSK_ATTR(n, t) \
-  if (hipError_t x = gsk_ffdwb_attr_r##n##_t##t(lds_total, &dmin); x != hipSuccess) e = x;
-#define GSK_ATTR2(n) GSK_ATTR(n, 0) GSK_ATTR(n, 1)
-  GSK_ATTR2(1) GSK_ATTR2(2) GSK_ATTR2(3) GSK_ATTR2(4) GSK_ATTR2(5) GSK_ATTR2(6) GSK_ATTR2(7) GSK_ATTR2(8)
-#undef GSK_ATTR2
-#undef GSK_ATTR
-  g_ffdwb_dyn_max = dmin;
-  return e;
-}
+extern "C" hipError_t gsk_init_ffdw_batch(uint32_t lds_total) { return gsk_set_lds(ffdwb_families(), lds_total, &g_ffdwb_dyn_max); }
 
 extern "C" uint32_t gsk_ffdw_batch_dyn_lds_max(void) { return g_ffdwb_dyn_max; }
 
@@ -127,15 +122,8 @@ extern "C" uint32_t gsk_ffdw_batch_dyn_lds_max(void) { return g_ffdwb_dyn_max; }
 extern "C" hipError_t gsk_ffdw_batch(const DevProblem* ds, uint32_t n, uint32_t R, uint32_t topo, uint32_t wide,
                                      uint32_t lds, hipStream_t s) {
   if (!n || lds > g_ffdwb_dyn_max) return hipErrorInvalidConfiguration;
-  switch (R * 2 + (topo ? 1 : 0)) {
-#define GSK_CASE(k)                                                    \
-  case 2 * k: return gsk_ffdwb_launch_r##k##_t0(ds, n, wide, lds, s); \
-  case 2 * k + 1: return gsk_ffdwb_launch_r##k##_t1(ds, n, wide, lds, s);
-    GSK_CASE(1) GSK_CASE(2) GSK_CASE(3) GSK_CASE(4) GSK_CASE(5) GSK_CASE(6) GSK_CASE(7) GSK_CASE(8)
-#undef GSK_CASE
-    default:
-      return hipErrorInvalidValue;
-  }
+  const GskWaveBatchFamily* f = gsk_family(ffdwb_families(), R, topo != 0);
+  return f ? f->launch(ds, n, wide, lds, s) : hipErrorInvalidValue;
 }
 
 // ===================================== consolidation simulations of n problems
@@ -179,47 +167,17 @@ extern "C" hipError_t gsk_trunc_sims_batch(const DevProblem* ds, uint32_t n, uin
   return hipGetLastError();
 }
 
-// The instantiations of the batched simulation kernel live in
-// ffd_sim_batch_r.hip, one translation unit per (R, TOPO): each exports its
-// launcher, its LDS attribute setter and its occupancy query.
-#define GSK_DECL(n, t)                                                                                                  \
-  extern "C" hipError_t gsk_ffdsb_launch_r##n##_t##t(const DevProblem* ds, const uint32_t* blocks, uint32_t cnt,        \
-                                                     uint32_t max_blocks, uint32_t nt, uint32_t lds, uint32_t ov_epoch, \
-                                                     hipStream_t s);                                                    \
-  extern "C" hipError_t gsk_ffdsb_attr_r##n##_t##t(uint32_t lds_total, uint32_t* dyn_min);                              \
-  extern "C" uint32_t gsk_ffdsb_occ_r##n##_t##t(uint32_t nt, uint32_t lds);
-#define GSK_DECL2(n) GSK_DECL(n, 0) GSK_DECL(n, 1)
-GSK_DECL2(1) GSK_DECL2(2) GSK_DECL2(3) GSK_DECL2(4) GSK_DECL2(5) GSK_DECL2(6) GSK_DECL2(7) GSK_DECL2(8)
-#undef GSK_DECL2
-#undef GSK_DECL
 static uint32_t g_ffdsb_dyn_max = 0;
 
-extern "C" hipError_t gsk_init_ffd_sim_batch(uint32_t lds_total) {
-  hipError_t e = hipSuccess;
-  uint32_t dmin = 0;
-#define GSK_ATTR(n, t) \
-  if (hipError_t x = gsk_ffdsb_attr_r##n##_t##t(lds_total, &dmin); x != hipSuccess) e = x;
-#define GSK_ATTR2(n) GSK_ATTR(n, 0) GSK_ATTR(n, 1)
-  GSK_ATTR2(1) GSK_ATTR2(2) GSK_ATTR2(3) GSK_ATTR2(4) GSK_ATTR2(5) GSK_ATTR2(6) GSK_ATTR2(7) GSK_ATTR2(8)
-#undef GSK_ATTR2
-#undef GSK_ATTR
-  g_ffdsb_dyn_max = dmin;
-  return e;
-}
+extern "C" hipError_t gsk_init_ffd_sim_batch(uint32_t lds_total) { return gsk_set_lds(ffdsb_families(), lds_total, &g_ffdsb_dyn_max); }
 
 extern "C" uint32_t gsk_ffd_sim_batch_dyn_lds_max(void) { return g_ffdsb_dyn_max; }
 
 // resident workgroups per CU of the batched simulation kernel (R resources,
 // the general variant or not, nt threads) at a dynamic LDS size; at least 1
 extern "C" uint32_t gsk_ffd_sim_batch_blocks_per_cu(uint32_t R, uint32_t lds, uint32_t nt, uint32_t general) {
-  uint32_t n = 0;
-  switch (R * 2 + (general ? 1 : 0)) {
-#define GSK_CASE(k)                                      \
-  case 2 * k: n = gsk_ffdsb_occ_r##k##_t0(nt, lds); break; \
-  case 2 * k + 1: n = gsk_ffdsb_occ_r##k##_t1(nt, lds); break;
-    GSK_CASE(1) GSK_CASE(2) GSK_CASE(3) GSK_CASE(4) GSK_CASE(5) GSK_CASE(6) GSK_CASE(7) GSK_CASE(8)
-#undef GSK_CASE
-  }
+  const GskSimBatchFamily* f = gsk_family(ffdsb_families(), R, general != 0);
+  const uint32_t n = f ? f->blocks_per_cu(nt, lds) : 0u;
   return n ? n : 1u;
 }
 
@@ -232,15 +190,8 @@ extern "C" hipError_t gsk_ffd_sim_batch(const DevProblem* ds, const uint32_t* bl
                                         hipStream_t s) {
   if (!n || n > 65535 || !max_blocks) return hipErrorInvalidValue;
   if (lds > g_ffdsb_dyn_max) return hipErrorInvalidConfiguration;
-  switch (R * 2 + (general ? 1 : 0)) {
-#define GSK_CASE(k)                                                                                \
-  case 2 * k: return gsk_ffdsb_launch_r##k##_t0(ds, blocks, n, max_blocks, nt, lds, ov_epoch, s); \
-  case 2 * k + 1: return gsk_ffdsb_launch_r##k##_t1(ds, blocks, n, max_blocks, nt, lds, ov_epoch, s);
-    GSK_CASE(1) GSK_CASE(2) GSK_CASE(3) GSK_CASE(4) GSK_CASE(5) GSK_CASE(6) GSK_CASE(7) GSK_CASE(8)
-#undef GSK_CASE
-    default:
-      return hipErrorInvalidValue;
-  }
+  const GskSimBatchFamily* f = gsk_family(ffdsb_families(), R, general != 0);
+  return f ? f->launch(ds, blocks, n, max_blocks, nt, lds, ov_epoch, s) : hipErrorInvalidValue;
 }
 
 // ===================== every slot's outcome in one pass (gs_batch_consolidate_fetch_all)

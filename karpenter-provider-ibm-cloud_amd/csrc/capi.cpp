@@ -1,5 +1,6 @@
 // capi.cpp — C-ABI of libgpusched.so (include/gpusched.h): context, HBM
 // buffers, kernel launches on one HIP stream, result decode.
+#include "batch_fetch_layout.hpp"
 #include "ctx.hpp"
 
 #include <set>
@@ -39,7 +40,7 @@ void upload_problem(gs_ctx* c, const SimPlan* sims, bool records) {
     // (single-wave kernel) the existing nodes' slack codes
     // (the block kernel's capacity; the single-wave kernel's is smaller by the
     // node codes -- a Solve that outgrows it reruns on the block kernel)
-    const uint32_t other = gsk_ffd_lds_bytes(0, (uint32_t)e.thr_val.size(), 0, gsd::topo_lds_bytes(e.TGZ, e.ZS, e.TGH, e.n_lazy)) + 8;
+    const uint32_t other = gsd::gsk_ffd_lds_bytes(0, (uint32_t)e.thr_val.size(), 0, gsd::topo_lds_bytes(e)) + 8;
     const uint32_t dyn = std::min(gsk_ffd_dyn_lds_max(), gsk_ffdw_dyn_lds_max());
     auto claims_fit = [&](uint32_t extra) {
       const uint32_t fit = dyn > other + extra ? (dyn - other - extra) / 23 : 0;
@@ -521,6 +522,47 @@ gs_status decode_result(gs_ctx* c, const SolveRecords& r, gs_result* out) {
   return GS_OK;
 }
 
+gs_status solve_status_error(gs_ctx* c, uint32_t status) {
+  if (status == gsd::ST_CLAIMS)
+    return fail(c, GS_E_CAPACITY, "NodeClaim count exceeded the device capacity (" +
+                                      std::to_string(c->ch ? std::min<uint32_t>(c->dp.claim_cap, 65535) : c->dp.max_claims) +
+                                      " in-flight NodeClaims)");
+  if (status == gsd::ST_POD_COUNT)
+    return fail(c, GS_E_CAPACITY, "a NodeClaim would hold more than 65535 pods (16-bit pod count in LDS)");
+  if (status == gsd::ST_INTERNAL) return fail(c, GS_E_HIP, "ffd kernel reported an internal error (queue / channel bound)");
+  return fail(c, GS_E_HIP, "ffd kernel reported an unknown status");
+}
+
+template <class H>
+void fill_solve_stats(const gs_ctx* c, const H& h, gs_result* out) {
+  const gsh::Encoded& e = c->enc;
+  out->checks = e.checks;
+  out->pops = h.pops;
+  out->cand_evals = h.cand_evals;
+  out->cand_full = h.cand_full;
+  out->claim_prefix = h.claim_prefix;
+  out->node_prefix = h.node_prefix;
+  // wall_clock64 runs at 100 MHz; ~0: the phase timers are not built in (-1)
+  auto phase_ms = [](uint64_t t) { return t == ~0ull ? -1.0 : (double)t * 1e-5; };
+  out->t_ffd_sort_ms = phase_ms(h.t_sort);
+  out->t_ffd_scan_ms = phase_ms(h.t_scan);
+  out->t_ffd_template_ms = phase_ms(h.t_tmpl);
+  out->sorts_fast = h.fast_sorts;
+  out->sorts_generic = h.generic_sorts;
+  out->words = e.W;
+  out->n_templates = e.T;
+  out->n_variants = e.V;
+  out->t_encode_ms = c->t_encode;
+  out->t_upload_ms = c->t_upload;
+  out->t_feas_ms = c->t_feas;
+  out->t_ffd_ms = c->t_ffd;
+  out->t_truncate_ms = c->t_trunc;
+  out->t_run_wall_ms = c->t_run_wall;
+  out->t_wall_ms = 0;
+}
+template void fill_solve_stats(const gs_ctx*, const gsd::Ctrl&, gs_result*);
+template void fill_solve_stats(const gs_ctx*, const gsbf::FetchHead&, gs_result*);
+
 }  // namespace gsc
 
 using namespace gsc;
@@ -794,14 +836,7 @@ gs_status gs_fetch(gs_ctx* c, gs_result* out) {
   } catch (const HipError& ex) {
     return fail(c, GS_E_HIP, ex.msg);
   }
-  if (c->ctrl.status == gsd::ST_CLAIMS)
-    return fail(c, GS_E_CAPACITY, "NodeClaim count exceeded the device capacity (" +
-                                      std::to_string(c->ch ? std::min<uint32_t>(c->dp.claim_cap, 65535) : c->dp.max_claims) +
-                                      " in-flight NodeClaims)");
-  if (c->ctrl.status == gsd::ST_POD_COUNT)
-    return fail(c, GS_E_CAPACITY, "a NodeClaim would hold more than 65535 pods (16-bit pod count in LDS)");
-  if (c->ctrl.status == gsd::ST_INTERNAL) return fail(c, GS_E_HIP, "ffd kernel reported an internal error (queue / channel bound)");
-  if (c->ctrl.status != 0) return fail(c, GS_E_HIP, "ffd kernel reported an unknown status");
+  if (c->ctrl.status != 0) return solve_status_error(c, c->ctrl.status);
   std::vector<uint32_t> unplaced;
   for (uint32_t i = 0; i < c->ctrl.qlen; i++) unplaced.push_back(queue[(c->ctrl.qhead + i) % e.P]);
   const SolveRecords rec{log.data(),       (uint32_t)log.size(),      hdr.data(), its.data(),           nits.data(), c->ctrl.n_claims,
@@ -809,31 +844,9 @@ gs_status gs_fetch(gs_ctx* c, gs_result* out) {
   const gs_status ds = decode_result(c, rec, out);
   if (ds != GS_OK) return ds;
   c->t_fetch = ms_since(t0);
-  out->checks = e.checks;
-  out->pops = c->ctrl.pops;
-  out->cand_evals = c->ctrl.cand_evals;
-  out->cand_full = c->ctrl.cand_full;
-  out->claim_prefix = c->ctrl.claim_prefix;
-  out->node_prefix = c->ctrl.node_prefix;
-  // wall_clock64 runs at 100 MHz; ~0: the phase timers are not built in (-1)
-  auto phase_ms = [](uint64_t t) { return t == ~0ull ? -1.0 : (double)t * 1e-5; };
-  out->t_ffd_sort_ms = phase_ms(c->ctrl.t_sort);
-  out->t_ffd_scan_ms = phase_ms(c->ctrl.t_scan);
-  out->t_ffd_template_ms = phase_ms(c->ctrl.t_tmpl);
-  out->sorts_fast = c->ctrl.fast_sorts;
-  out->sorts_generic = c->ctrl.generic_sorts;
-  out->words = e.W;
-  out->n_templates = e.T;
-  out->n_variants = e.V;
-  out->t_encode_ms = c->t_encode;
-  out->t_upload_ms = c->t_upload;
-  out->t_feas_ms = c->t_feas;
-  out->t_ffd_ms = c->t_ffd;
-  out->t_truncate_ms = c->t_trunc;
+  fill_solve_stats(c, c->ctrl, out);
   out->t_fetch_ms = c->t_fetch;
   out->t_total_ms = c->t_encode + c->t_upload + c->t_feas + c->t_ffd + c->t_trunc + c->t_fetch;
-  out->t_run_wall_ms = c->t_run_wall;
-  out->t_wall_ms = 0;
   return GS_OK;
 }
 

@@ -322,9 +322,10 @@ gs_status cons_plan_sets(gs_ctx* c, std::string* err) {
 gs_status cons_plan_grid(gs_ctx* c, const SimBudget* budget, std::string* err) {
   SimPlan& sp = c->sims;
   const gsh::Encoded& e = c->enc;
-  const uint32_t lds = gsk_ffd_lds_bytes(std::max<uint32_t>(sp.max_pods, 1), (uint32_t)e.thr_val.size(),
-                                         (e.NN + 31) / 32, gsd::topo_lds_bytes(e.TGZ, e.ZS, e.TGH, e.n_lazy)) +
-                       8u * gsd::ovh_slots_for(sp.ov_cap);
+  // (upload_problem gives the problem these sizes: max_claims, nb_words, ovh_slots)
+  const uint32_t max_claims = std::max<uint32_t>(sp.max_pods, 1), ovh_slots = gsd::ovh_slots_for(sp.ov_cap);
+  const uint32_t base = gsd::gsk_ffd_lds_bytes(max_claims, (uint32_t)e.thr_val.size(), (e.NN + 31) / 32, gsd::topo_lds_bytes(e));
+  const uint32_t lds = gsd::sim_lds_bytes(base, ovh_slots, max_claims, false);
   if (lds > gsk_ffd_dyn_lds_max()) {
     *err = "simulation exceeds the workgroup LDS (pods per simulation or state nodes)";
     return GS_E_CAPACITY;
@@ -336,12 +337,12 @@ gs_status cons_plan_grid(gs_ctx* c, const SimBudget* budget, std::string* err) {
   // many simulations: the narrow workgroup (throughput); few: the wide one
   // (each simulation's latency) -- ffd.hip FB_SIM / FB_SIM_NARROW
   sp.nt = budget ? budget->nt : cons_sim_threads(sp.evaluated.size(), cus);
-  const bool general = e.TG || e.any_mv || e.any_vol;
+  const bool general = gsd::general_variant(e);
   auto occupancy = budget ? gsk_ffd_sim_batch_blocks_per_cu : gsk_ffd_sim_blocks_per_cu;
   uint32_t per_cu = occupancy(e.R, lds, sp.nt, general ? 1u : 0u);
   // the simulations' queue arrays and add logs in LDS when that costs no
   // resident workgroup (ffd.hip s_simq / s_simlog)
-  const uint32_t lds_q = lds + 32u * std::max<uint32_t>(sp.max_pods, 1);
+  const uint32_t lds_q = gsd::sim_lds_bytes(base, ovh_slots, max_claims, true);
   sp.sim_lds = false;
   if (lds_q <= gsk_ffd_dyn_lds_max() && occupancy(e.R, lds_q, sp.nt, general ? 1u : 0u) >= per_cu) {
     sp.sim_lds = true;
@@ -495,6 +496,16 @@ gs_status cons_fetch_decide(gs_ctx* c, gs_consolidation_result* out) {
   return GS_OK;
 }
 
+// A simulation that did not end well (status: its control status, or 0 where
+// its record counts are out of bounds): the failure, after the counts of a
+// kernel that stopped are reset
+static gs_status sim_status_error(gs_ctx* c, uint32_t status) {
+  if (status != 0) reset_sim_counts(c);
+  if (status == gsd::ST_POD_COUNT)
+    return fail(c, GS_E_CAPACITY, "a simulated NodeClaim would hold more than 65535 pods (16-bit pod count)");
+  return fail(c, GS_E_HIP, "simulation kernel reported an internal error");
+}
+
 // ... decide from records: computeConsolidation per evaluated simulation
 // (rec[k]; its options at opts[rec[k].opt_off ...]), then the mode's policy.
 // The one statement of the decision rules: the per-slot fetch above and
@@ -515,10 +526,7 @@ gs_status cons_decide_records(gs_ctx* c, const gsd::SimOut* rec, const gsd::OptP
   for (size_t k = 0; k < NS; k++) {
     const uint32_t s = sp.evaluated[k];
     const gsd::SimOut& h = rec[k];
-    if (h.status != 0) reset_sim_counts(c);
-    if (h.status == gsd::ST_POD_COUNT)
-      return fail(c, GS_E_CAPACITY, "a simulated NodeClaim would hold more than 65535 pods (16-bit pod count)");
-    if (h.status != 0) return fail(c, GS_E_HIP, "simulation kernel reported an internal error");
+    if (h.status != 0) return sim_status_error(c, h.status);
     const uint32_t q0 = sp.pod_off[k], P = sp.pod_off[k + 1] - q0;
     checks += (uint64_t)P * (e.NN - sp.sets[s].size() + e.checks_per_pod);
     gs_command& cmd = c->commands[s];
@@ -575,8 +583,7 @@ gs_status cons_decide_records(gs_ctx* c, const gsd::SimOut* rec, const gsd::OptP
     // RemoveInstanceTypeOptionsByPriceAndMinValues over the OrderByPrice list
     // (the price filter, then SatisfiesMinValues on what is left); an option's
     // price is its cheapest available offering's on the claim's grid (minp)
-    if (h.tmpl >= e.tmpl.size() || h.n_opt > gsd::SIM_OPTS_MAX)
-      return fail(c, GS_E_HIP, "simulation kernel reported an internal error");
+    if (h.tmpl >= e.tmpl.size() || h.n_opt > gsd::SIM_OPTS_MAX) return sim_status_error(c, 0);
     const uint32_t ob = (uint32_t)c->cmd_options.size();
     for (uint32_t i = 0; i < h.n_opt; i++) {
       const gsd::OptPair& o = opts[h.opt_off + i];
@@ -696,11 +703,7 @@ gs_status cons_sim_results(gs_ctx* c, uint32_t sim, gs_result* out) {
   try {
     HIPCHK(hipMemcpy(&ct, c->dp.sim_ctrl + k, sizeof ct, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(&blk, c->dp.sim_blk, sizeof blk, hipMemcpyDeviceToHost));
-    if (ct.status != 0) reset_sim_counts(c);
-    if (ct.status == gsd::ST_POD_COUNT)
-      return fail(c, GS_E_CAPACITY, "a simulated NodeClaim would hold more than 65535 pods (16-bit pod count)");
-    if (ct.status != 0 || ct.n_log > P || ct.n_claims > P)
-      return fail(c, GS_E_HIP, "simulation kernel reported an internal error");
+    if (ct.status != 0 || ct.n_log > P || ct.n_claims > P) return sim_status_error(c, ct.status);
     const uint32_t M = ct.n_claims;
     log.resize(ct.n_log);
     hdr.resize(M);

@@ -19,53 +19,8 @@
 #include "../../include/gpusched.h"
 #include "encode.hpp"
 #include "growbuf.hpp"
+#include "kernel_api.hpp"
 #include "layout.hpp"
-
-extern "C" hipError_t gsk_init_trunc(uint32_t trunc_lds_bytes);
-extern "C" hipError_t gsk_init_ffd(uint32_t lds_total);
-extern "C" uint32_t gsk_ffd_dyn_lds_max(void);
-extern "C" uint32_t gsk_ffd_sim_blocks_per_cu(uint32_t R, uint32_t lds, uint32_t nt, uint32_t general);
-extern "C" uint32_t gsk_ffd_lds_bytes(uint32_t max_claims, uint32_t nthr, uint32_t nb_words,
-                                      uint32_t topo_bytes);
-extern "C" hipError_t gsk_feas(const gsd::DevProblem* d, uint32_t apply_limits, uint32_t w_lo, uint32_t w_hi,
-                               hipStream_t s);
-extern "C" hipError_t gsk_ffd(const gsd::DevProblem* d, uint32_t blocks, hipStream_t s);
-extern "C" hipError_t gsk_init_ffdw(uint32_t lds_total);
-extern "C" uint32_t gsk_ffdw_dyn_lds_max(void);
-extern "C" hipError_t gsk_ffdw(const gsd::DevProblem* d, uint32_t ch, hipStream_t s);
-extern "C" hipError_t gsk_trunc(const gsd::DevProblem* d, uint32_t lds_bytes, uint32_t n_slots, hipStream_t s);
-extern "C" hipError_t gsk_trunc_slots(const gsd::DevProblem* d, uint32_t lds_bytes, uint32_t slot0, uint32_t n_slots,
-                                      hipStream_t s);
-extern "C" hipError_t gsk_mv_rows(const gsd::DevProblem* d, hipStream_t s);
-extern "C" hipError_t gsk_queue_records(const gsd::DevProblem* d, hipStream_t s);
-extern "C" hipError_t gsk_merge_shards(const gsd::ShardMerge* m, hipStream_t s);
-// batch_kernels.hip: the grid kernels over a device array of problems
-extern "C" hipError_t gsk_init_batch(uint32_t trunc_lds_bytes);
-extern "C" uint32_t gsk_feas_lp(uint32_t W);
-extern "C" hipError_t gsk_feas_batch(const gsd::DevProblem* ds, uint32_t n, uint32_t lp, uint64_t max_cursors,
-                                     uint64_t max_pairs, hipStream_t s);
-extern "C" hipError_t gsk_init_state_batch(const gsd::DevProblem* ds, uint32_t n, hipStream_t s);
-extern "C" hipError_t gsk_queue_records_batch(const gsd::DevProblem* ds, uint32_t n, uint32_t max_pods, hipStream_t s);
-extern "C" hipError_t gsk_init_ffdw_batch(uint32_t lds_total);
-extern "C" uint32_t gsk_ffdw_batch_dyn_lds_max(void);
-extern "C" hipError_t gsk_ffdw_batch(const gsd::DevProblem* ds, uint32_t n, uint32_t R, uint32_t topo, uint32_t wide,
-                                     uint32_t lds, hipStream_t s);
-extern "C" hipError_t gsk_trunc_batch(const gsd::DevProblem* ds, uint32_t n, uint32_t max_slots, uint32_t lds_bytes,
-                                      hipStream_t s);
-// ... and the consolidation simulations of a device array of problems
-extern "C" hipError_t gsk_init_ffd_sim_batch(uint32_t lds_total);
-extern "C" uint32_t gsk_ffd_sim_batch_dyn_lds_max(void);
-extern "C" uint32_t gsk_ffd_sim_batch_blocks_per_cu(uint32_t R, uint32_t lds, uint32_t nt, uint32_t general);
-extern "C" hipError_t gsk_sim_begin_batch(const gsd::DevProblem* ds, const uint32_t* blocks, uint32_t n,
-                                          uint32_t clear_overlays, hipStream_t s);
-extern "C" hipError_t gsk_ffd_sim_batch(const gsd::DevProblem* ds, const uint32_t* blocks, uint32_t n, uint32_t max_blocks,
-                                        uint32_t R, uint32_t general, uint32_t nt, uint32_t lds, uint32_t ov_epoch,
-                                        hipStream_t s);
-extern "C" hipError_t gsk_trunc_sims_batch(const gsd::DevProblem* ds, uint32_t n, uint32_t mv, uint32_t max_sims,
-                                           uint32_t max_slots, uint32_t lds_bytes, hipStream_t s);
-extern "C" hipError_t gsk_cons_gather_batch(const gsd::DevProblem* ds, const uint32_t* blocks, const uint32_t* sim_base,
-                                            uint32_t n, uint32_t max_sims, gsd::SlotOut* slots, gsd::SimOut* recs,
-                                            gsd::OptPair* opts, uint32_t* cursor, hipStream_t s);
 
 namespace gsc {
 
@@ -330,6 +285,13 @@ struct SolveRecords {
   const uint32_t* node_index;
 };
 gs_status decode_result(gs_ctx* c, const SolveRecords& r, gs_result* out);
+// The fetch epilogue gs_fetch and gs_batch_fetch_all (batch.cpp) share:
+// the failure a Solve's non-zero control status stands for, and the counters,
+// phase timers, sizes and stage times of a fetched Solve.  H: gsd::Ctrl or
+// gsbf::FetchHead (the same field names).
+gs_status solve_status_error(gs_ctx* c, uint32_t status);
+template <class H>
+void fill_solve_stats(const gs_ctx* c, const H& h, gs_result* out);  // capi.cpp instantiates both
 // multi.cpp: gs_consolidation_results on the shard that evaluated `sim`
 gs_status sharded_results(gs_ctx* c, uint32_t sim, gs_result* out);
 uint32_t trunc_lds_bytes(uint32_t N);

@@ -46,7 +46,6 @@ constexpr int NWAVE_MAX = FB_MAX / 64;
 #endif
 constexpr int SEQ_SORT = GS_SEQ_SORT;  // subranges up to this length sort on thread 0
 
-constexpr uint32_t WREG = 4;  // option words a scoring lane keeps in registers
 enum : uint32_t { MOD_NONE = 0, MOD_INC = 1, MOD_APPEND = 2 };
 
 

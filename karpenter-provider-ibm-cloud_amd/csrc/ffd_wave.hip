@@ -2,6 +2,7 @@
 // the launcher (the kernel template is in ffd_wave.hpp, its instantiations
 // in ffd_wave_r.hip) and the autoplacement ranking sort.
 #include "ffd_wave.hpp"
+#include "kernel_api.hpp"
 
 using namespace gsd;
 
@@ -11,56 +12,30 @@ using namespace gsd;
 
 // ---------------------------------------------------------------- launchers
 // The kernel instantiations live in ffd_wave_r.hip, one translation unit per
-// (R, TOPO): each exports its launcher and its LDS attribute setter.
-extern "C" uint32_t gsk_ffd_lds_bytes(uint32_t max_claims, uint32_t nthr, uint32_t nb_words,
-                                      uint32_t topo_bytes);
-#define GSK_DECL(n, t)                                                                                  \
-  extern "C" hipError_t gsk_ffdw_launch_r##n##_t##t(const DevProblem* d, uint32_t mode, uint32_t lds, hipStream_t s); \
-  extern "C" hipError_t gsk_ffdw_attr_r##n##_t##t(uint32_t lds_total, uint32_t* dyn_min);
-#define GSK_DECL2(n) GSK_DECL(n, 0) GSK_DECL(n, 1)
-GSK_DECL2(1) GSK_DECL2(2) GSK_DECL2(3) GSK_DECL2(4) GSK_DECL2(5) GSK_DECL2(6) GSK_DECL2(7) GSK_DECL2(8)
-#undef GSK_DECL2
-#undef GSK_DECL
+// (R, TOPO): each exports its family record (kernel_api.hpp).
+static auto& ffdw_families() {
+#define GSK_ENTRY(r, t) GSK_RT_NAME(gsk_ffdw, r, t)(),
+  static const GskWaveFamily* const table[] = {GSK_FOR_EACH_RT(GSK_ENTRY)};
+#undef GSK_ENTRY
+  return table;
+}
 static uint32_t g_ffdw_dyn_max = 0;
 
-extern "C" hipError_t gsk_init_ffdw(uint32_t lds_total) {
-  hipError_t e = hipSuccess;
-  uint32_t dmin = 0;
-#define GSK_ATTR(n, t) \
-  if (hipError_t x = gsk_ffdw_attr_r##n##_t##t(lds_total, &dmin); x != hipSuccess) e = x;
-#define GSK_ATTR2(n) GSK_ATTR(n, 0) GSK_ATTR(n, 1)
-  GSK_ATTR2(1) GSK_ATTR2(2) GSK_ATTR2(3) GSK_ATTR2(4) GSK_ATTR2(5) GSK_ATTR2(6) GSK_ATTR2(7) GSK_ATTR2(8)
-#undef GSK_ATTR2
-#undef GSK_ATTR
-  g_ffdw_dyn_max = dmin;
-  return e;
-}
+extern "C" hipError_t gsk_init_ffdw(uint32_t lds_total) { return gsk_set_lds(ffdw_families(), lds_total, &g_ffdw_dyn_max); }
 
 extern "C" uint32_t gsk_ffdw_dyn_lds_max(void) { return g_ffdw_dyn_max; }
-
-// whether option rows of W words take the wide instantiation (a batch groups its problems by it)
-extern "C" uint32_t gsk_ffdw_wide(uint32_t W) { return W > WREG ? 1u : 0u; }
 
 // the single-wave provisioning Solve: grid-wide state reset, then one wave;
 // ch: the claim scan state in HBM (d->ch_* allocated, claim_cap slots)
 extern "C" hipError_t gsk_ffdw(const DevProblem* d, uint32_t ch, hipStream_t s) {
-  const uint32_t lds = gsk_ffd_lds_bytes(ch ? 0u : d->max_claims_wave, d->n_thr, 0, topo_lds_bytes(d->TGZ, d->ZS, d->TGH, d->n_lazy)) +
-                       wave_node_lds_bytes(d->NN);
+  const uint32_t lds = wave_lds_bytes(*d, ch != 0);
   if (lds > g_ffdw_dyn_max) return hipErrorInvalidConfiguration;
   if (d->n_sims) return hipErrorInvalidValue;
   if (ch && !(d->ch_slk && d->ch_rm && d->ch_so && d->ch_scr && d->ch_tmpl)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(ffd_init_kernel, dim3(256), dim3(256), 0, s, *d);
-  const bool topo = d->TG || d->any_mv || d->any_vol;
-  const uint32_t mode = (ch ? 1u : 0u) | (d->W > WREG ? 2u : 0u);
-  switch (d->R * 2 + (topo ? 1 : 0)) {
-#define GSK_CASE(n)                                                     \
-  case 2 * n: return gsk_ffdw_launch_r##n##_t0(d, mode, lds, s);        \
-  case 2 * n + 1: return gsk_ffdw_launch_r##n##_t1(d, mode, lds, s);
-    GSK_CASE(1) GSK_CASE(2) GSK_CASE(3) GSK_CASE(4) GSK_CASE(5) GSK_CASE(6) GSK_CASE(7) GSK_CASE(8)
-#undef GSK_CASE
-    default:
-      return hipErrorInvalidValue;
-  }
+  const GskWaveFamily* f = gsk_family(ffdw_families(), d->R, general_variant(*d));
+  if (!f) return hipErrorInvalidValue;
+  return f->launch(d, (ch ? 1u : 0u) | (wide_rows(d->W) ? 2u : 0u), lds, s);
 }
 
 // ------------------------------------------------ autoplacement ranking sort

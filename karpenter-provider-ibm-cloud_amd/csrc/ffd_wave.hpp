@@ -51,7 +51,6 @@ static_assert(offsetof(VarRec, fk_begin) == 4 && offsetof(VarRec, fk_count) == 8
               "VarRec dword map used by ffdw_kernel");
 static_assert(offsetof(ClaimRec, maxa) == 128, "ClaimRec maxa after two 64-B lines");
 
-constexpr uint32_t WREG = 4;  // option words a scoring lane keeps in registers
 // solver <-> memory-agent wave channels (LDS)
 #ifndef GS_RING
 #define GS_RING 16

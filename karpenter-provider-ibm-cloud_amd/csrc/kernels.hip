@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "devutil.hpp"
+#include "kernel_api.hpp"
 #include "layout.hpp"
 
 using namespace gsd;

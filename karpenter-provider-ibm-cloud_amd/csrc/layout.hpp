@@ -461,6 +461,50 @@ struct DevProblem {
   uint32_t sim_lds;            // simulations keep queue / staleness / variant / add log in LDS (32 B per pod)
 };
 
+// ------------------------------------------------------------- launch rules
+// Which instantiation of a Solve kernel a problem runs and how much dynamic LDS
+// its launch requests: stated here once, for the launchers and for the host
+// code that groups problems by instantiation or asks whether one fits.  X is a
+// DevProblem or the encoder's gsh::Encoded (the same field names).
+
+// the general variant (TOPO): topology groups, minValues or volume limits
+template <class X>
+inline bool general_variant(const X& x) {
+  return x.TG || x.any_mv || x.any_vol;
+}
+constexpr uint32_t WREG = 4;  // option words a scoring lane keeps in registers
+// option rows of W words take the wide instantiation of the single-wave Solve
+inline bool wide_rows(uint32_t W) { return W > WREG; }
+
+template <class X>
+inline uint32_t topo_lds_bytes(const X& x) {
+  return topo_lds_bytes(x.TGZ, x.ZS, x.TGH, x.n_lazy);
+}
+// the block Solve: slack + room u64, ord/sc/scr u16, tmpl u8 per claim,
+// thresholds, (simulations) the touched-node bitmap, and the topology spread
+// state (known domains, per-pod minimum, zone counts) of TG groups
+inline uint32_t gsk_ffd_lds_bytes(uint32_t max_claims, uint32_t nthr, uint32_t nb_words, uint32_t topo_bytes) {
+  const uint32_t thr = nthr + 4;
+  const uint32_t base = (((23u * max_claims + 7u) & ~7u) + thr * 8u + nb_words * 4u + 7u) & ~7u;
+  return base + topo_bytes;
+}
+inline uint32_t block_lds_bytes(const DevProblem& d) {
+  return gsk_ffd_lds_bytes(d.max_claims, d.n_thr, d.nb_words, topo_lds_bytes(d));
+}
+// a simulation launch: the block Solve's `base`, the overlay hash and, with
+// `queue`, the simulations' queue arrays and add log (32 B per pod)
+inline uint32_t sim_lds_bytes(uint32_t base, uint32_t ovh_slots, uint32_t max_claims, bool queue) {
+  return base + 8u * ovh_slots + (queue ? 32u * max_claims : 0u);
+}
+inline uint32_t sim_lds_bytes(const DevProblem& d) {
+  return sim_lds_bytes(block_lds_bytes(d), d.ovh_slots, d.max_claims, d.sim_lds != 0);
+}
+// the single-wave Solve: the existing nodes' codes beside the block Solve's
+// state without the node bitmap; ch: the claim scan state in HBM (no claims in LDS)
+inline uint32_t wave_lds_bytes(const DevProblem& d, bool ch) {
+  return gsk_ffd_lds_bytes(ch ? 0u : d.max_claims_wave, d.n_thr, 0, topo_lds_bytes(d)) + wave_node_lds_bytes(d.NN);
+}
+
 // the parent-side merge of a sharded static matrix (kernels.hip
 // merge_shards_kernel): the shards' device buffers and word slices
 constexpr int SHARDS_MAX = 16;

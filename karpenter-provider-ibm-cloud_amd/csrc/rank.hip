@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/gpusched.h"
+#include "kernel_api.hpp"  // gsk_rank_sort (ffd_wave.hip)
 #include "rank_rules.hpp"
 
 static_assert(gsr::kArchAny == GS_ARCH_ANY, "rank_rules.hpp arch wildcard");
@@ -133,9 +134,6 @@ __global__ __launch_bounds__(RK_NT) void rank_gather_kernel(RankArgs a) {
 }
 
 }  // namespace
-
-extern "C" hipError_t gsk_rank_sort(uint16_t* keys, uint16_t* pos, const uint32_t* np, uint32_t cap, int x,
-                                    hipStream_t s);
 
 extern "C" gs_status gs_rank_instance_types(uint32_t n, const int64_t* cpu_milli, const int64_t* memory_bytes,
                                             const double* price, const uint32_t* arch, uint32_t want_arch,
